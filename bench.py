@@ -14,6 +14,8 @@ per-GPU work shrinks with N).  Consecutive frames alternate over two HIP streams
 paths drain while the next frame fills the GPU and its gather overlaps rendering.
 
 Prints ONE JSON line on rank 0 (see DESIGN.md §Measurement for every field).
+A plain run sets up, warms up, times the steps, writes `--dump-outputs` and prints
+the line; the side legs (CPU baseline, C++ drop-in) run only with `--full`.
 """
 from __future__ import annotations
 
@@ -104,7 +106,7 @@ _T_START = time.perf_counter()
 
 def progress(msg: str) -> None:
     """A progress line on stderr (the JSON line stays the only stdout line): a long
-    default run -- CPU baseline, drop-in processes -- keeps showing it is alive."""
+    --full run -- CPU baseline, drop-in processes -- keeps showing it is alive."""
     print(f"[bench {time.perf_counter() - _T_START:7.1f} s] {msg}", file=sys.stderr, flush=True)
 
 
@@ -215,6 +217,26 @@ def dropin_bench(w, h, spp, bounces, frames, tcs, env=None):
     return out
 
 
+DUMP_BUDGET_BYTES = 60_000_000  # --dump-outputs: all arrays together (the limit is 64 MB of files)
+DUMP_SEED = 0
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: each array as <dirname>/<name>.npy in float32.  An array over its
+    share of the budget is cut to a fixed sample of its rows (elements of a 1-D array):
+    indices drawn once from DUMP_SEED, ascending, so two runs keep the same ones."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // len(arrays)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        row_bytes = 4 * int(np.prod(a.shape[1:], dtype=np.int64))
+        keep = share // row_bytes
+        if a.shape[0] > keep:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.shape[0], keep, replace=False))
+            a = a[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a.astype(np.float32))
+
+
 def profile_record(config):
     """Per-launch PMC counters and in-kernel lane counts of the render kernel for a
     config, from profiles/counters.json (rocprofv3 --pmc passes and the SPT_DIAG build,
@@ -308,15 +330,24 @@ def main():
                          "fails)")
     ap.add_argument("--cpu-spp", type=int, default=0,
                     help="spp of the CPU-baseline sample (0: the config's own spp on config 2, scaled down on others)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-dropin", action="store_true", help="skip the C++ drop-in measurement (config 2)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the side legs: the CPU baseline and (config 2) the "
+                         "C++ drop-in measurement; a plain run times its steps and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-dropin", action="store_true", help="--full: skip the C++ drop-in measurement (config 2)")
     ap.add_argument("--dropin-frames", type=int, default=20)
     ap.add_argument("--dump", default="", help="write rank 0's final g_data bytes to this file")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step returned (rank 0's frame: float RGBA per pixel, and "
+                         "g_data: RGB8 bytes) as DIR/frame.npy and DIR/g_data.npy, float32; outputs over the "
+                         "64 MB budget as a fixed seeded sample of their rows")
     ap.add_argument("--launch-check", action="store_true",
                     help="only start the ranks and report the process group (launcher test; no GPU work)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args, sys.argv[1:]))
     if args.launch_check:
@@ -482,6 +513,9 @@ def main():
 
     total_samples = W * H * spp * args.steps
     value = total_samples / elapsed / 1e6
+    if rank == 0 and args.dump_outputs:
+        last = bufs[(counter[0] - 1) % nst]  # the last timed step's buffers (synchronised above)
+        dump_outputs(args.dump_outputs, {"frame": last["frame"].cpu().numpy(), "g_data": last["g_data"].cpu().numpy()})
     if rank == 0:
         # dominant kernel = render_kernel; per-launch averages from HIP events on `stream`
         launches = max(st["launches"], 1)
@@ -603,7 +637,7 @@ def main():
                 if k in rk:
                     rv[k] = rk[k]
             out["roofline_valu"] = rv
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # config 2 at its own 100 spp; the larger configs at their scene and depth, on
             # config 2's frame, with spp scaled down to a bounded sample (c5's 10 000
             # spheres are scanned brute force by the reference's loop)
@@ -611,7 +645,7 @@ def main():
             cw, ch = (W, H) if args.config in ("c1", "c2") else (1200, 800)
             progress("timed region done; CPU baseline")
             out["cpu_baseline"] = cpu_baseline(scene, view, cw, ch, cpu_spp, bounces)
-        if world == 1 and args.config == "c2" and not args.no_dropin and args.engine == "megakernel":
+        if args.full and world == 1 and args.config == "c2" and not args.no_dropin and args.engine == "megakernel":
             # the drop-in boundary itself: RenderSegment/RenderSegmentTask from RenderJob threads
             progress("C++ drop-in legs")
             try:

@@ -8,9 +8,9 @@
 #          gpu          pytest -m gpu (the whole GPU suite)
 #          mr           bench.py --gpus 2 rehearsals (gloo ranks on one GPU, launches and service)
 #          smoke        __graft_entry__.smoke()
-#          bench        python bench.py (default arguments: config 2, service on)
-#          bench0       python bench.py --service 0 (one launch per frame)
-#          benchq       bench.py without the CPU baseline and drop-in legs (quick)
+#          bench        python bench.py --full (config 2 with the CPU baseline and drop-in legs)
+#          bench0       python bench.py --full --service 0 (one launch per frame)
+#          benchq       bench.py without the CPU baseline and drop-in legs (a plain run, quick)
 #          bench0q      the same with --service 0
 #          c5 / c3      bench.py --config c5 / c3 (quick legs)
 #          scaling      tools/scaling_probe.py --streams 2 (service on and off)
@@ -58,9 +58,9 @@ for step in "$@"; do
     diag_nol) SPT_PRIM_LISTS=0 SPT_LIB=libspt_hip_diag.so run diag_nol 200 python tools/diag.py c2 --json "gpurun_out/${TAG}_diag_nol_c2.json" ;;
     mr) run mr 300 $PYT -v -m gpu tests/test_gpu_parity.py -k two_ranks ;;
     smoke) run smoke 120 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 400 python bench.py ;;
+    bench) run bench 400 python bench.py --full ;;
     bench1q) run bench1q 120 python bench.py --no-cpu-baseline --no-dropin --service 1 ;;
-    bench0) run bench0 400 python bench.py --service 0 ;;
+    bench0) run bench0 400 python bench.py --full --service 0 ;;
     benchq) run benchq 120 python bench.py --no-cpu-baseline --no-dropin ;;
     bench0q) run bench0q 120 python bench.py --no-cpu-baseline --no-dropin --service 0 ;;
     c5_nol) SPT_PRIM_LISTS=0 run c5_nol 300 python bench.py --config c5 --steps 4 --warmup 1 --no-cpu-baseline --no-dropin ;;
