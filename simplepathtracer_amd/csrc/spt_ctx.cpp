@@ -42,10 +42,7 @@ void warm_start(spt_ctx *ctx)
     // the member's own device (a multi-device context's members: the caller's current
     // device is another member's)
     if (hipSetDevice(ctx->device) != hipSuccess) return;  // no warm streams: created on first use
-    int lo = 0, hi = 0;
-    (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-    int prio = lo;  // the read-ahead parts' priority (spec_stream)
-    if (const char *e = env_var("SPT_READAHEAD_PRIO")) prio = std::atoi(e);
+    const int prio = readahead_prio();  // the read-ahead parts' streams
     for (int i = 0; i < 1 + SpecFrame::kParts; ++i) {
         hipStream_t s = nullptr;
         const hipError_t e = i == 0 ? hipStreamCreateWithFlags(&s, hipStreamNonBlocking)
@@ -555,7 +552,7 @@ int spt_set_camera_one(spt_ctx *ctx, const float view[16], const float eye[4], c
 int spt_set_params_one(spt_ctx *ctx, uint32_t width, uint32_t height, uint32_t spp, uint32_t bounces, uint64_t seed)
 {
     if (!ctx) return fail(nullptr, SPT_ERR_ARG, "null context");
-    std::lock_guard<std::mutex> lk(ctx->mu);
+    std::unique_lock<std::mutex> lk(ctx->mu);
     if (int rc_ = svc_end(ctx)) return rc_;  // the session holds the state this setter changes
     ctx->gen++;                              // a read-ahead frame of the old state is stale
     if (width == 0 || height == 0) return fail(ctx, SPT_ERR_ARG, "empty frame %ux%u", width, height);
@@ -570,11 +567,13 @@ int spt_set_params_one(spt_ctx *ctx, uint32_t width, uint32_t height, uint32_t s
     ctx->seed = seed;
     ctx->params_set = true;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int rc = rebuild_prim(ctx);
     // the drop-in (spt_prepare_dropin) renders its first frame through the tiling read-ahead:
-    // its page-locked frame now, with the setup, not in that frame
-    if (ctx->spec.arm_first && ctx->readahead)
-        (void)spec_frame_bytes(ctx, (size_t)width * height * 3);  // best effort: else at arming
-    return rebuild_prim(ctx);
+    // its page-locked frame now, with the setup, not in that frame.  Last, once the context
+    // is whole again, as it may wait unlocked for serves in progress; best effort: else at
+    // the first tile-shaped call
+    if (ctx->spec.st.arm_first() && ctx->readahead) (void)spec_frame_bytes(ctx, lk, (size_t)width * height * 3);
+    return rc;
 }
 
 int spt_set_cluster_size_one(spt_ctx *ctx, uint32_t k)
@@ -876,21 +875,8 @@ void spt_ctx_destroy(spt_ctx *ctx)
         if (h->stream) (void)hipStreamDestroy(h->stream);
         delete h;
     }
-    for (BatchSet &b : ctx->spec.bs) {
-        if (b.d_rects) (void)hipFree(b.d_rects);
-        if (b.h_rects) (void)hipHostFree(b.h_rects);
-        if (b.d_stage) (void)hipFree(b.d_stage);
-        if (b.stream) (void)hipStreamDestroy(b.stream);
-    }
-    for (hipEvent_t e : ctx->spec.ev)
-        if (e) (void)hipEventDestroy(e);
-    if (ctx->spec.h8) (void)hipHostFree(ctx->spec.h8);
-    for (BatchSet &b : ctx->bsets) {
-        if (b.d_rects) (void)hipFree(b.d_rects);
-        if (b.h_rects) (void)hipHostFree(b.h_rects);
-        if (b.d_stage) (void)hipFree(b.d_stage);
-        if (b.stream) (void)hipStreamDestroy(b.stream);
-    }
+    spec_destroy(ctx);
+    for (BatchSet &b : ctx->bsets) destroy_batch_set(&b);
     for (void *b : {(void *)ctx->d_tile, (void *)ctx->d_fullframe})
         if (b) (void)hipFree(b);
     if (ctx->frame_ev) (void)hipEventDestroy(ctx->frame_ev);
@@ -960,7 +946,7 @@ int spt_prepare_dropin(spt_ctx *ctx)
     return for_members(ctx, [&](spt_ctx *c) {
         std::lock_guard<std::mutex> lk(c->mu);
         warm_start(c);
-        c->spec.arm_first = first;
+        c->spec.st.set_arm_first(first);
         return SPT_OK;
     });
 }

@@ -2,7 +2,9 @@
 // units (round 6: spt_api.cpp split along its sections, no behaviour change):
 //   spt_ctx.cpp      context, setters, scene / accel / primary-list uploads, stats
 //   spt_render.cpp   render_impl (render + fold launches), host calls, rows / samples entry points
-//   spt_batch.cpp    batched host calls and the tiling read-ahead (SpecFrame)
+//   spt_batch.cpp    batched host calls (render_batched, launch_batch)
+//   spt_readahead.cpp the tiling read-ahead's HIP half (SpecFrame); spt_readahead.h is its
+//                    HIP-free half (tile recognition, bookkeeping, reader gate)
 //   spt_service.cpp  the render service's host half (sessions, publication, flow control)
 //   spt_multi.cpp    multi-device frames (spt_render_frame) and page-locked g_data
 // The context owns the device copy of the reference's global state (scene SoA, camera,
@@ -14,6 +16,7 @@
 #include "spt_hip.h"
 #include "spt_accel.h"
 #include "spt_internal.h"
+#include "spt_readahead.h"
 
 #include <hip/hip_runtime.h>
 
@@ -42,6 +45,13 @@ inline const char *env_var(const char *name)
 {
     const char *e = std::getenv(name);
     return e && *e ? e : nullptr;
+}
+
+// Rows y in [yB, yE) of the frame live at g_data rows H-1-y: one band of pitch W * 3 bytes
+// that starts here, column xB on
+inline size_t band_offset(uint32_t W, uint32_t H, uint32_t yE, uint32_t xB)
+{
+    return ((size_t)(H - yE) * W + xB) * 3;
 }
 
 extern thread_local std::string g_thread_error;
@@ -103,16 +113,7 @@ struct BatchReq {
 // waits for its part and copies its own rows to the caller's g_data.  Every tile is still
 // rendered once per frame; nothing is written to the caller's buffer before its call.
 struct SpecFrame {
-    bool active = false;
-    int mode = 0;
-    uint32_t tc = 0, sw = 0, sh = 0;
-    uint64_t gen = 0;            // spt_ctx::gen when launched
-    std::vector<uint8_t> served; // per tile (row-major over tile rows j, columns i)
-    // per tile, calls still owed by an earlier frame of this tiling: tiles that frame had
-    // not served when the next one began -- a RenderJob thread that starts only after its
-    // frame's final wait ended (Renderer.hpp:242-255, 282-292) -- served from the current
-    // frame (same state, the same bytes) instead of starting another one
-    std::vector<uint8_t> owed;
+    ReadAhead st;  // the current frame's tiles and the arming (spt_readahead.h)
     static constexpr int kParts = 4;
     uint32_t parts = 4, rows_per_part = 1;  // tile rows per launch
     hipEvent_t ev[kParts] = {};
@@ -121,22 +122,13 @@ struct SpecFrame {
     BatchSet bs[kParts];
     // the frame's RGB8 bytes (g_data layout) in page-locked host memory: the parts' folds
     // write them through its device view, each serve copies its tile's rows on the host
-    // (a hipMemcpy2D per tile cost ~10 us of runtime time each: 1 024 per frame at tc = 32)
+    // (a hipMemcpy2D per tile cost ~10 us of runtime time each: 1 024 per frame at tc = 32);
+    // freed and reallocated by spec_frame_bytes alone
     uint8_t *h8 = nullptr, *h8_dev = nullptr;
     size_t h8_cap = 0;
     // serves copying out of h8 with the context unlocked: the next read-ahead neither
-    // rewrites nor reallocates h8 before they are done (readers_cv, ctx->mu)
-    uint32_t readers = 0;
-    std::condition_variable readers_cv;
-    // arming: the tiles of one tiling (mode, tc, frame size) called so far by plain calls
-    int arm_mode = -1;
-    uint32_t arm_tc = 0, arm_w = 0, arm_h = 0, arm_count = 0;
-    std::vector<uint8_t> arm_seen;
-    bool armed = false;
-    // arm at a tiling's first call instead of after a whole tiling (the drop-in,
-    // spt_prepare_dropin: its caller is RenderImageParallelMain, which renders every tile
-    // of every frame -- and MainLoop only one frame per process)
-    bool arm_first = false;
+    // rewrites nor reallocates h8 before they are done
+    ReaderGate gate;
 };
 
 constexpr int kSpecMiss = 1;  // spec_serve: not a read-ahead tile (render it as usual)
@@ -482,14 +474,14 @@ int render_impl(spt_ctx *ctx, int mode, const spt::RowMap &map, float4 *d_rgba, 
 int render_task_range(spt_ctx *ctx, uint32_t i0, uint32_t i1, float4 *d_out, hipStream_t s);
 spt::FoldArgs fold_args(const spt_ctx *ctx, const uint32_t *samples, uint32_t slot_words);
 int spec_serve(spt_ctx *ctx, std::unique_lock<std::mutex> &lk, int mode, uint32_t yB, uint32_t yE, uint32_t xB, uint32_t xE, uint8_t *g_data);
-int spec_frame_bytes(spt_ctx *ctx, size_t bytes);
-int spec_launch(spt_ctx *ctx, std::unique_lock<std::mutex> &lk, int mode, uint32_t tc);
-int spec_prepare(spt_ctx *ctx, std::unique_lock<std::mutex> &lk, int mode, uint32_t tc);
-int spec_stream(spt_ctx *ctx, int p);
-int spec_drain(spt_ctx *ctx);
+int spec_frame_bytes(spt_ctx *ctx, std::unique_lock<std::mutex> &lk, size_t bytes);
+void spec_destroy(spt_ctx *ctx);
+int readahead_prio();
 int render_batched(spt_ctx *ctx, std::unique_lock<std::mutex> &lk, int mode, uint32_t yB, uint32_t yE, uint32_t xB, uint32_t xE, float *rgba, uint8_t *g_data);
 int launch_batch(spt_ctx *ctx, BatchSet *bs, const std::vector<BatchReq *> &batch, uint8_t *spec_d8 = nullptr);
 uint64_t batch_slot_bytes(const spt_ctx *ctx, int mode, uint64_t npix);
+int grow_host_rects(spt_ctx *ctx, BatchSet *bs, size_t n);
+void destroy_batch_set(BatchSet *b);
 int reset_one(spt_ctx *ctx);
 int stats_one(spt_ctx *ctx, spt_stats *out);
 

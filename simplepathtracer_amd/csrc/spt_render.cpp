@@ -344,9 +344,7 @@ int render_segment_host(spt_ctx *ctx, int mode, uint32_t yB, uint32_t yE, uint32
         if (rgba)
             HIP_TRY(ctx, hipMemcpyAsync(rgba, hs->d_stage, npix * sizeof(float4), hipMemcpyDeviceToHost, hs->stream));
         if (g_data) {
-            // rows y in [yB, yE) live at g_data rows H-1-y: one contiguous band, xB.. per row
-            const size_t pitch = (size_t)W * 3;
-            const size_t off = (size_t)(H - yE) * pitch + (size_t)xB * 3;
+            const size_t pitch = (size_t)W * 3, off = band_offset(W, H, yE, xB);
             HIP_TRY(ctx, hipMemcpy2DAsync(g_data + off, pitch, d8 + off, pitch, (size_t)w * 3, h,
                                           hipMemcpyDeviceToHost, hs->stream));
         }

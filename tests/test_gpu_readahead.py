@@ -1,4 +1,4 @@
-"""GPU tests of the drop-in's tiling read-ahead (spt_batch.cpp SpecFrame):
+"""GPU tests of the drop-in's tiling read-ahead (spt_readahead.cpp SpecFrame):
 RenderSegment / RenderSegmentTask calls over the reference's tc x tc tiling
 (Renderer.hpp:264-273, MakeRenderSegmentData), g_data only, are served from one
 read-ahead render of the whole tiling, once the caller has called every tile of that
@@ -225,3 +225,38 @@ def test_late_call_is_served_without_another_frame(spt, golden_scenes):
     assert np.array_equal(g1, want) and np.array_equal(g2, want)
     parts = min(4, tc)
     assert st["batches"] == 2 * parts and st["batched_calls"] == 2 * tc * tc, st
+
+
+def test_frame_growth_between_readahead_frames(spt, golden_scenes, monkeypatch):
+    """set_params to a larger frame after a read-ahead frame has been served: the first
+    tile-shaped call at the new size grows the page-locked frame, the tiling of the new size
+    arms and is served, and every byte equals plain calls.  No successful call leaves an
+    error behind (the best-effort allocation paths report none)."""
+    W0, H0, W, H, spp, tc = 160, 96, 240, 160, 4, 2
+    ctx = make_ctx(spt, golden_scenes, W0, H0, spp, seed=4)
+    last_error = lambda: spt.lib().spt_last_error(ctx.handle)  # noqa: E731
+
+    class Checked:
+        def render_segment(self, *a, **kw):
+            ctx.render_segment(*a, **kw)
+            assert last_error() == b"", last_error()
+
+    render_tiling(Checked(), W0, H0, tc, False, 2)  # plain calls: arms the tiling
+    small = render_tiling(Checked(), W0, H0, tc, False, 2)  # one read-ahead frame
+    ctx.set_params(W, H, spp, 50, 4)
+    assert last_error() == b"", last_error()
+    ctx.reset_stats()
+    frames = [render_tiling(Checked(), W, H, tc, False, 2) for _ in range(2)]
+    st = ctx.stats()
+    ctx.close()
+    monkeypatch.setenv("SPT_READAHEAD", "0")
+    for (w, h), got in (((W0, H0), [small]), ((W, H), frames)):
+        plain = make_ctx(spt, golden_scenes, w, h, spp, seed=4)
+        want = np.zeros(w * h * 3, np.uint8)
+        for t in tiles(w, h, tc):
+            plain.render_segment(*t, g_data=want, rgba=False)
+        plain.close()
+        for k, g in enumerate(got):
+            assert np.array_equal(g, want), f"{w}x{h} frame {k}: {np.count_nonzero(g != want)} bytes differ"
+    # the arming frame tile by tile, the second in the read-ahead's launches
+    assert st["samples"] == 2 * W * H * spp and st["batched_calls"] == 2 * tc * tc
