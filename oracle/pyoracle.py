@@ -67,6 +67,10 @@ def lib():
         L.spo_find_closest.argtypes = [P, P, P]; L.spo_find_closest.restype = u32
         L.spo_write_pixel.argtypes = [P, P]; L.spo_write_pixel.restype = None
         L.spo_trace_sample.argtypes = [P, P, u32, u32, u32, ctypes.c_int, P]; L.spo_trace_sample.restype = u32
+        L.spo_trace_sample_info.argtypes = [P, P, u32, u32, u32, ctypes.c_int, P, P]
+        L.spo_trace_sample_info.restype = u32
+        L.spo_probe_sphere.argtypes = [P, u32, P, P, P]; L.spo_probe_sphere.restype = ctypes.c_int
+        L.spo_schlick_log.argtypes = [P, u32]; L.spo_schlick_log.restype = u32
         L.spo_primary_winners.argtypes = [P, P, P, u32, P]; L.spo_primary_winners.restype = None
         for fn in (L.spo_render_segment, L.spo_render_segment_task):
             fn.argtypes = [P, P, u32, u32, u32, u32, P, P]; fn.restype = u64
@@ -150,6 +154,58 @@ def trace_sample(scene: OracleScene, frame: Frame, x, y, s, task=False):
     out = np.zeros(4, np.float32)
     casts = lib().spo_trace_sample(scene.ref, ctypes.byref(frame), x, y, s, int(task), _p(out))
     return out, casts
+
+
+def trace_sample_info(scene: OracleScene, frame: Frame, x, y, s, task=False):
+    """trace_sample, and the path's specular-event count and task-mode dropped flag."""
+    out = np.zeros(4, np.float32)
+    info = np.zeros(2, np.uint32)
+    casts = lib().spo_trace_sample_info(scene.ref, ctypes.byref(frame), x, y, s, int(task), _p(out), _p(info))
+    return out, casts, int(info[0]), bool(info[1])
+
+
+def trace_region(scene: OracleScene, frame: Frame, yB, yE, xB, xE, task=False):
+    """Every sample of a region: colours (pixels, spp, 4), and per sample the ray count,
+    the specular-event count and the dropped flag (each (pixels, spp))."""
+    n, spp = (yE - yB) * (xE - xB), frame.spp
+    col = np.zeros((n, spp, 4), np.float32)
+    casts = np.zeros((n, spp), np.uint32)
+    info = np.zeros((n, spp, 2), np.uint32)
+    fn, sc, fr = lib().spo_trace_sample_info, scene.ref, ctypes.byref(frame)
+    f4, u4 = col.strides[1], info.strides[1]
+    pc, pi = col.ctypes.data, info.ctypes.data
+    for p in range(n):
+        y, x = yB + p // (xE - xB), xB + p % (xE - xB)
+        for s in range(spp):
+            k = p * spp + s
+            casts[p, s] = fn(sc, fr, x, y, s, int(task), pc + k * f4, pi + k * u4)
+    return col, casts, info[:, :, 0], info[:, :, 1].astype(bool)
+
+
+def probe_sphere(scene: OracleScene, i, d, o):
+    """Sphere i alone on the ray (o, d): (RaySphereIntersection passes, squared distance
+    find_closest would compare, contact ahead of the origin)."""
+    d = np.ascontiguousarray(d, np.float32); o = np.ascontiguousarray(o, np.float32)
+    out = np.zeros(2, np.float32)
+    ok = lib().spo_probe_sphere(scene.ref, int(i), _p(d), _p(o), _p(out))
+    return bool(ok), out[0], bool(out[1])
+
+
+def find_closest(scene: OracleScene, d, o) -> int:
+    d = np.ascontiguousarray(d, np.float32); o = np.ascontiguousarray(o, np.float32)
+    return int(lib().spo_find_closest(scene.ref, _p(d), _p(o)))
+
+
+def schlick_bases(fn, cap=1 << 20) -> np.ndarray:
+    """The 1 - c arguments of every Schlick powf(1 - c, 5) the oracle evaluates while fn()
+    runs on this thread."""
+    buf = np.zeros(cap, np.float32)
+    lib().spo_schlick_log(_p(buf), cap)
+    try:
+        fn()
+    finally:
+        n = lib().spo_schlick_log(None, 0)
+    return buf[:min(n, cap)]
 
 
 def primary_winners(scene: OracleScene, frame: Frame, xys) -> np.ndarray:

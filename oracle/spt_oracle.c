@@ -226,6 +226,19 @@ uint32_t spo_find_closest(const spo_scene *sc, const float d[4], const float o[4
     return find_closest(sc, ld4w(d), ld4w(o));
 }
 
+/* What find_closest sees of sphere i alone on the ray (o, d): returns whether
+ * RaySphereIntersection passes; out[0] = the squared distance it would compare with
+ * min_d, out[1] = 1 if the contact lies ahead (Collision.hpp:98), else 0. */
+int spo_probe_sphere(const spo_scene *sc, uint32_t i, const float d4[4], const float o4[4], float out[2])
+{
+    v4 d = ld4w(d4), o = ld4w(o4), c = center(sc, i);
+    float r = sc->radii[i];
+    v4 p = closest_contact(c, r, o, d);
+    out[0] = vlensq(vsub(o, p));
+    out[1] = vdot(o, d) < vdot(p, d) ? 1.f : 0.f;
+    return ray_sphere(c, r, d, o);
+}
+
 /* IOHelpers.hpp:17-22 WritePixel: uint8(round(sqrt(c/255)*255)) per channel, no
  * clamp.  static_cast<uint8_t>(float) is emitted by gcc/clang on x86-64 as
  * cvttss2si (int32, INT_MIN for NaN/out of range) then the low byte. */
@@ -312,8 +325,26 @@ static v4 sample_reflective(tctx *t, v4 d, v4 o, uint32_t bounce, uint32_t idx)
  * (oracle/probe_overloads.cpp).  So Schlick, the total-internal-reflection test
  * and the Snell scalar are all float: glibc's powf (called here, as the
  * reference's __builtin_powf does) and the correctly rounded sqrtf. */
+static __thread float *schlick_log;
+static __thread uint32_t schlick_cap, schlick_n;
+/* Record the base 1 - c of every Schlick powf of this thread's traces into buf (NULL:
+ * stop); returns how many the previous buffer received (those past cap are counted,
+ * not stored). */
+uint32_t spo_schlick_log(float *buf, uint32_t cap)
+{
+    uint32_t n = schlick_n;
+    schlick_log = buf;
+    schlick_cap = cap;
+    schlick_n = 0;
+    return n;
+}
+
 static inline float schlick_of(float rsq, float c)
 {
+    if (schlick_log) {
+        if (schlick_n < schlick_cap) schlick_log[schlick_n] = 1.f - c;
+        schlick_n++;
+    }
     return rsq + (1.f - rsq) * powf(1.f - c, 5.f);
 }
 static inline int no_tir(float r, float c)
@@ -409,6 +440,19 @@ uint32_t spo_trace_sample(const spo_scene *sc, const spo_frame *fr, uint32_t x, 
     v4 c = trace(&t, d, ld4(fr->eye), fr->bounces);
     if (task_mode) c.w = t.dropped ? 0.0f : 1.0f;
     st4(out, c);
+    return t.casts;
+}
+
+uint32_t spo_trace_sample_info(const spo_scene *sc, const spo_frame *fr, uint32_t x, uint32_t y, uint32_t s,
+                               int task_mode, float out[4], uint32_t info[2])
+{
+    tctx t = {sc, fr, spo_sample_key(fr->seed, y * fr->width + x, s), 0, 0, task_mode, 0};
+    v4 d = primary_dir(fr, &t.st, x, y);
+    v4 c = trace(&t, d, ld4(fr->eye), fr->bounces);
+    if (task_mode) c.w = t.dropped ? 0.0f : 1.0f;
+    st4(out, c);
+    info[0] = t.spec;
+    info[1] = (uint32_t)t.dropped;
     return t.casts;
 }
 

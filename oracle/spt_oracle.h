@@ -86,6 +86,10 @@ void spo_matvec(const float m[16], const float v[4], float out[4]);
 void spo_camera_basis(const float eye[4], const float look_at[4], const float up[4], float view_out[16]);
 uint32_t spo_find_closest(const spo_scene *sc, const float d[4], const float o[4]);
 void spo_write_pixel(const float c[4], uint8_t out[3]);
+/* Sphere i alone on the ray (o, d), as find_closest sees it: returns whether
+ * RaySphereIntersection passes; out[0] = the squared distance compared with min_d,
+ * out[1] = 1 if the contact lies ahead of the origin (Collision.hpp:98). */
+int spo_probe_sphere(const spo_scene *sc, uint32_t i, const float d[4], const float o[4], float out[2]);
 
 /* ---- render loop (SingleThreadPathTracer.hpp, TaskBasedPathTracer.hpp) ---- */
 /* One (pixel, sample) path of RenderSegment: out[0..3] = color, returns number
@@ -94,6 +98,13 @@ void spo_write_pixel(const float c[4], uint8_t out[3]);
 void spo_primary_winners(const spo_scene *sc, const spo_frame *fr, const uint32_t *xys, uint32_t n, uint32_t *winner);
 uint32_t spo_trace_sample(const spo_scene *sc, const spo_frame *fr, uint32_t x, uint32_t y,
                           uint32_t s, int task_mode, float out[4]);
+/* spo_trace_sample, and info[0] = the path's specular events (the one that meets
+ * SPO_SPECULAR_CAP or the pass cap included), info[1] = 1 if task mode dropped it. */
+uint32_t spo_trace_sample_info(const spo_scene *sc, const spo_frame *fr, uint32_t x, uint32_t y,
+                               uint32_t s, int task_mode, float out[4], uint32_t info[2]);
+/* Record the base 1 - c of every Schlick powf(1 - c, 5) traced by the calling thread
+ * into buf (NULL stops); returns the count since the previous call (may exceed cap). */
+uint32_t spo_schlick_log(float *buf, uint32_t cap);
 /* RenderSegment over [yB,yE)x[xB,xE).  rgba: region-local float4 per pixel
  * (row-major), rgb8: full-frame g_data in the reference index layout.  Either may
  * be NULL. Returns total FindClosest calls. */

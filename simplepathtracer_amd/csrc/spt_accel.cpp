@@ -355,6 +355,13 @@ AccelTables build_accel(const float *centers4, const float *radii, uint32_t n, u
             const double cbb = (double)nd.cx * nd.cx + (double)nd.cy * nd.cy + (double)nd.cz * nd.cz;
             nd.cb2 = (float)(kFlatScale * cbb);
             nd.rb = round_up((double)nd.k1 + 4e-6 * cbb - (double)nd.cb2);
+            if (!(std::sqrt(cbb) + rb <= 1e15)) {
+                // squares near the float range (K1, c |Cb|^2 overflow and K1'' = inf - inf):
+                // the node never culls, like the tree boxes and the member pretest past 1e15
+                nd.cx = nd.cy = nd.cz = 0.f;
+                nd.cb2 = 0.f;
+                nd.k1 = nd.rb = INFINITY;
+            }
         };
         // Preorder emission, once per direction octant: siblings are ordered front to
         // back along the octant's diagonal, so a wave walking the layout of its

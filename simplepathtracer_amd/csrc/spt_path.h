@@ -545,9 +545,10 @@ __device__ __forceinline__ Hit find_closest(const AccelView &ac, const f3 &o, co
             const float w = __builtin_fmaf(bx, osx, __builtin_fmaf(by, osy, __builtin_fmaf(bz, osz, qoe)));
             return __builtin_fmaf(-tcb, tcb, w);
         };
-        // the node's mask (vs K1'') and leaf test; `x` from node_x(r)
+        // the node's mask (vs K1'') and leaf test; `x` from node_x(r).  A NaN x (|o|^2 or
+        // tcb^2 overflowed: inf - inf) keeps the node: only a proven miss culls
         auto finish = [&](const uint32_t *r, float x) {
-            const unsigned long long mm = __ballot(x <= __uint_as_float(r[6]));
+            const unsigned long long mm = __ballot(!(x > __uint_as_float(r[6])));
             diag_node(mm);
             if (mm != 0ull) test_leaf_pre<LEAF>(slots, (cfloat *)ac.kpre, ac.orig, r[5], o, d, dod, pl, h, dg);
         };

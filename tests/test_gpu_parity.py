@@ -82,6 +82,10 @@ def test_device_numerics_match_host(ctx, oracle):
     libm.powf.argtypes = [ctypes.c_float, ctypes.c_float]
     c_any = u.view(np.float32)
     hard = [float.fromhex(h) for h in ("0x1.003bap-24", "0x1.14708ep-1", "0x1.ef5ee8p-1", "0x1.14708ep+0")]
+    # Schlick's bases 1 - c on the degenerate scenes (read from the oracle on the CPU,
+    # tests/test_degenerate_oracle.py: both extremes; none leaves [0, 1])
+    from degenerate_scenes import SCHLICK_BASES
+    hard += [float.fromhex(h) for h in SCHLICK_BASES]
     for i in list(range(0, n, 7)) + [n - 8 + k for k in range(8)]:
         assert out[i, 2] == np.float32(libm.powf(float(a[i]), 5.0)), ("powf(x,5)", a[i])
         want = np.float32(libm.powf(float(c_any[i]), 5.0))
