@@ -103,6 +103,59 @@ __host__ __device__ inline uint32_t row_of_fast(const RowMap &m, uint32_t lr, co
     return m.y0 + (blk * m.parts + m.part) * m.strip + (lr - blk * m.strip);
 }
 
+// The sampler's dealing of a wave's 64 lanes to its np (1..64) pending lanes
+// (coop_ball_vector, spt_path.h): with q = 64 / np and rem = 64 - q * np, pending ranks
+// below rem get q + 1 consecutive lanes and the others q, so every lane works and the
+// trial counts differ by at most one.  A rank's lanes are contiguous: its segment of the
+// acceptance ballot is one shift of the 64-bit mask.  np is wave-uniform, so its rule
+// is one scalar load from a 65-entry constant table (no division anywhere): `below`
+// has bit p set when lane p + 1 starts a rank's segment, so the rank a lane helps is
+// the count of set bits below the lane.
+struct DealRule {
+    uint64_t below;
+    uint32_t q, rem;
+};
+constexpr DealRule make_deal_rule(uint32_t np)
+{
+    DealRule r{0ull, 0u, 0u};
+    if (np == 0u || np > 64u) return r;
+    r.q = 64u / np;
+    r.rem = 64u - r.q * np;
+    uint32_t start = 0;
+    for (uint32_t k = 0; k < np; ++k) {
+        if (start > 0u) r.below |= 1ull << (start - 1u);
+        start += r.q + (k < r.rem ? 1u : 0u);
+    }
+    return r;
+}
+struct DealTable {
+    DealRule e[65];
+    constexpr DealTable() : e{}
+    {
+        for (uint32_t np = 0; np <= 64u; ++np) e[np] = make_deal_rule(np);
+    }
+};
+static constexpr DealTable kDealTable{};
+// first lane and lane count of pending rank `rank` (< np)
+__host__ __device__ inline uint32_t deal_start(const DealRule &r, uint32_t rank)
+{
+    return rank * r.q + (rank < r.rem ? rank : r.rem);
+}
+__host__ __device__ inline uint32_t deal_count(const DealRule &r, uint32_t rank)
+{
+    return r.q + (rank < r.rem ? 1u : 0u);
+}
+// the pending rank `lane` helps and its trial offset within that rank's lanes
+__host__ __device__ inline void deal_lane(const DealRule &r, uint32_t lane, uint32_t &rank, uint32_t &tt)
+{
+#ifdef __HIP_DEVICE_COMPILE__
+    rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(r.below >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)r.below, 0u));
+#else
+    rank = (uint32_t)__builtin_popcountll(r.below & ((1ull << lane) - 1ull));
+#endif
+    tt = lane - deal_start(r, rank);
+}
+
 // (sample, pixel) of the q-th item of a batch of S samples over a region of
 // `rows` x `width` pixels, items ordered [8-row band][8-column tile][sample]
 // [pixel in tile] (ragged tiles at the right and bottom edges).  A claim of

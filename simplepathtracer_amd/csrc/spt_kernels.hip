@@ -110,7 +110,7 @@ constexpr uint32_t kGlaneMaxNodes = SPT_GLANE_MAX_NODES;
 // slot, bounce, phase | spec << 2; the render service adds its job's counter (word 12).
 constexpr uint32_t kParkWords = 12;
 template <bool JOB = false>
-__device__ __forceinline__ void park_path(uint32_t *q, uint32_t row, const Path &ps)
+__device__ __forceinline__ void park_path(uint32_t *q, int32_t row, const Path &ps)
 {
     if (JOB) q[12 * 64 + row] = ps.job;
     q[0 * 64 + row] = ps.item;
@@ -127,7 +127,7 @@ __device__ __forceinline__ void park_path(uint32_t *q, uint32_t row, const Path 
     q[11 * 64 + row] = ps.phase | (ps.spec << 2);
 }
 template <bool JOB = false>
-__device__ __forceinline__ void unpark_path(const uint32_t *q, uint32_t row, Path &ps)
+__device__ __forceinline__ void unpark_path(const uint32_t *q, int32_t row, Path &ps)
 {
     if (JOB) ps.job = q[12 * 64 + row];
     ps.item = q[0 * 64 + row];
@@ -560,7 +560,10 @@ __device__ __forceinline__ void render_body(const RenderArgs &a)
     constexpr bool PRIM = SPT_PRIM && !LDSN && !GLANE;
     constexpr uint32_t PW = kParkWords + (SVC ? 1u : 0u);  // parked words per path
     __shared__ uint32_t s_park[PRIM ? (BLOCK / 64u) * PW * 64u : 1];
-    uint32_t *const park = s_park + (PRIM ? (threadIdx.x >> 6) * PW * 64u : 0u);
+    // the lane's own row of the wave's rows; row r is addressed from it as r - lane, so that
+    // the rows' base is not a second register live for the whole kernel (it went to scratch)
+    uint32_t *const park = s_park + (PRIM ? opaque_v((threadIdx.x >> 6) * PW * 64u + lane) : 0u);
+    auto prow = [&](uint32_t r) -> int32_t { return (int32_t)r - (int32_t)lane; };
     // SVC: the wave's copy of its current job's record (svc_find_job, words 0-23) and its
     // claim state (words kSvcSt..31: kept in LDS, not SGPRs, since only claims read them)
     __shared__ uint32_t s_rec[SVC ? (BLOCK / 64u) * kSvcRecWords : 1];
@@ -740,7 +743,7 @@ __device__ __forceinline__ void render_body(const RenderArgs &a)
                 const uint32_t cnt = (uint32_t)__popcll(need);
                 const uint32_t rank = lane_rank(need);
                 const uint32_t take = min(cnt, q_n - q_pos);
-                if (ps.phase == PH_IDLE && rank < take) unpark_path<SVC>(park, q_pos + rank, ps);
+                if (ps.phase == PH_IDLE && rank < take) unpark_path<SVC>(park, prow(q_pos + rank), ps);
                 q_pos += take;
                 bool more = !exhausted;
                 if (SVC && cnt > take) {
@@ -750,7 +753,7 @@ __device__ __forceinline__ void render_body(const RenderArgs &a)
                 if (cnt > take && more) {
                     // the queue is empty: park every lane's own path in its own row and
                     // start 64 new paths (wave-uniform)
-                    park_path<SVC>(park, lane, ps);
+                    park_path<SVC>(park, 0, ps);
                     // the own path lives in LDS across the batch, not in registers
                     asm volatile("" ::: "memory");
                     ps.phase = PH_IDLE;
@@ -819,7 +822,7 @@ __device__ __forceinline__ void render_body(const RenderArgs &a)
         if (live == 0ull) {
             if (PRIM && prim_iter) {
                 // no item was left for the batch: the lanes' own paths back
-                unpark_path<SVC>(park, lane, ps);
+                unpark_path<SVC>(park, 0, ps);
                 q_n = q_pos = 0;
                 continue;
             }
@@ -1006,10 +1009,10 @@ __device__ __forceinline__ void render_body(const RenderArgs &a)
             // rows [0, n) of the queue (a lane writes row rank <= lane, after the whole
             // wave has read its own row: LDS operations of a wave complete in order)
             Path own;
-            unpark_path<SVC>(park, lane, own);
+            unpark_path<SVC>(park, 0, own);
             __builtin_amdgcn_wave_barrier();
             const unsigned long long lv = __ballot(ps.phase != PH_IDLE);
-            if (ps.phase != PH_IDLE) park_path<SVC>(park, lane_rank(lv), ps);
+            if (ps.phase != PH_IDLE) park_path<SVC>(park, prow(lane_rank(lv)), ps);
             ps = own;
             q_n = (uint32_t)__popcll(lv);
             q_pos = 0;

@@ -35,6 +35,11 @@
 #ifndef SPT_SAMPLER_SKIP0
 #define SPT_SAMPLER_SKIP0 1
 #endif
+// The sampler's cooperative rounds deal all 64 lanes to the pending lanes as evenly as
+// possible (DealRule, spt_internal.h); 0: powers of two, at most 16 helpers each
+#ifndef SPT_SAMPLER_EVEN
+#define SPT_SAMPLER_EVEN 1
+#endif
 // wave walk: leaves entered by at most 8 lanes are tested as dealt (lane, member) pairs
 // (test_leaf_pairs); 2: also those entered by 9-16 lanes, two members per lane
 #ifndef SPT_LEAF_PAIRS
@@ -932,11 +937,16 @@ struct Path {
 // GenerateUniformDistInsideSphereVector (Random.hpp:115-127) for every lane with
 // `need`, all 64 lanes cooperating.  The stream is counter-based (draw n of a lane
 // is mix(st0 + (n+1) gamma)), so trial j = draws 3j..3j+2 can be evaluated by any
-// lane.  Round 0: every lane runs its own trial 0.  Later rounds: each still
-// pending lane gets H helper lanes (H = the largest power of two <= 64 / pending,
-// at most 16) that evaluate its trials jb .. jb+H-1 at once; it takes the lowest
-// accepted one.  The result and the advanced state st0 + 3 (j* + 1) gamma equal
-// the sequential loop's.  Must be called in wave-uniform control flow.
+// lane.  Round 0: every lane runs its own trial 0.  Later rounds: the 64 lanes are
+// dealt to the np still pending lanes as evenly as possible (DealRule, spt_internal.h:
+// 64 / np consecutive lanes each, one more for the first 64 mod np; no lane idles),
+// and a pending lane's helpers evaluate its next trials j .. j + count - 1 at once; it
+// takes the lowest accepted one, else adds count to its own j (trial counts differ per
+// lane, so j travels to the helpers beside the lane id).  With SPT_SAMPLER_EVEN 0 each
+// pending lane gets H = the largest power of two <= 64 / np, at most 16, helpers and
+// the trial base jb is common.  Either way a lane's trials are evaluated in whole
+// prefixes, so the result and the advanced state st0 + 3 (j* + 1) gamma equal the
+// sequential loop's.  Must be called in wave-uniform control flow, all 64 lanes active.
 // `lds`: 64 words of wave-private LDS.
 __device__ __forceinline__ f3 coop_ball_vector(uint64_t &st, bool need, uint32_t *lds, unsigned long long *rounds = nullptr)
 {
@@ -966,6 +976,39 @@ __device__ __forceinline__ f3 coop_ball_vector(uint64_t &st, bool need, uint32_t
 #if SPT_DIAG
     const unsigned long long t_in = __builtin_amdgcn_s_memtime();
 #endif
+#if SPT_SAMPLER_EVEN
+    // jacc of a pending lane: its trials done so far (the next one's index), then its
+    // accepted trial's index; it travels to the helpers beside the lane id
+    if (jb != 0u) jacc = __builtin_amdgcn_inverse_ballot_w64(pend) ? 1u : 0u;
+    while (pend != 0ull) {
+        if (SPT_DIAG && rounds) rounds[1] += 1;  // cooperative rounds after round 0
+        const DealRule dr = kDealTable.e[__popcll(pend)];  // wave-uniform: one scalar load
+        const bool is_p = __builtin_amdgcn_inverse_ballot_w64(pend);
+        const uint32_t rank = lane_rank(pend);
+        if (is_p) lds[rank] = (jacc << 6) | lane;
+        uint32_t pidx, tt;
+        deal_lane(dr, lane, pidx, tt);
+        const uint32_t w = lds[pidx];
+        const uint32_t src = w & 63u;
+        const uint32_t h_lo = (uint32_t)__shfl((int)s_lo, (int)src), h_hi = (uint32_t)__shfl((int)s_hi, (int)src);
+        uint64_t b = (((uint64_t)h_hi << 32) | h_lo) + (uint64_t)(3u * ((w >> 6) + tt)) * kGamma;
+        f3 c;
+        c.x = uniform(b, -0.5f, 0.5f);
+        c.y = uniform(b, -0.5f, 0.5f);
+        c.z = uniform(b, -0.5f, 0.5f);
+        const unsigned long long acc = __ballot(!(lensq(c) < 0.25f));
+        // the pending lane's own segment of the ballot: its lowest accepted trial, if any
+        const uint32_t start = deal_start(dr, rank), cnt = deal_count(dr, rank);
+        const unsigned long long seg = acc >> (start & 63u);
+        const uint32_t tstar = seg != 0ull ? (uint32_t)__builtin_ctzll(seg) : 64u;
+        const bool found = is_p && tstar < cnt;
+        const uint32_t from = found ? start + tstar : lane;
+        const float rx = __shfl(c.x, (int)from), ry = __shfl(c.y, (int)from), rz = __shfl(c.z, (int)from);
+        if (found) r = mk(rx, ry, rz);
+        if (is_p) jacc += tstar < cnt ? tstar : cnt;
+        pend = __ballot(is_p && !found);
+    }
+#else
     while (pend != 0ull) {
         if (SPT_DIAG && rounds) rounds[1] += 1;  // cooperative rounds after round 0
         const uint32_t np = (uint32_t)__popcll(pend);
@@ -999,6 +1042,7 @@ __device__ __forceinline__ f3 coop_ball_vector(uint64_t &st, bool need, uint32_t
         pend = __ballot(is_p && !found);
         jb += 1u << lg;
     }
+#endif
     if (need) st = st0 + (uint64_t)(3u * (jacc + 1u)) * kGamma;
 #if SPT_DIAG
     if (rounds) rounds[2] += __builtin_amdgcn_s_memtime() - t_in;  // sampler cycles

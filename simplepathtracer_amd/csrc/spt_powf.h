@@ -115,6 +115,25 @@ SPT_POWF_HD inline int checkint(uint32_t iy)
 }
 SPT_POWF_HD inline bool zeroinfnan(uint32_t ix) { return 2u * ix - 1u >= 2u * 0x7f800000u - 1u; }
 
+// A polynomial coefficient formed where it is used.  In a kernel the compiler otherwise
+// hoists the coefficients that are fma addends into vector registers for the kernel's
+// whole lifetime and then spills them to scratch; two scalar moves it may not move
+// keep them out of both.  Same value on the host.
+#if defined(__HIP_DEVICE_COMPILE__)
+template <uint64_t BITS>
+__device__ __forceinline__ double lit_bits()
+{
+    uint32_t lo, hi;
+    asm volatile("s_mov_b32 %0, %2\n\ts_mov_b32 %1, %3"
+                 : "=s"(lo), "=s"(hi)
+                 : "i"((uint32_t)BITS), "i"((uint32_t)(BITS >> 32)));
+    return u2d(((uint64_t)hi << 32) | lo);
+}
+#define SPT_POWF_LIT(c) (::spt_powf_detail::lit_bits<__builtin_bit_cast(uint64_t, (double)(c))>())
+#else
+#define SPT_POWF_LIT(c) (c)
+#endif
+
 }  // namespace spt_powf_detail
 
 // powf(x, y) of glibc 2.35 (FMA variant) for finite nonzero y and any x; the
@@ -157,8 +176,8 @@ SPT_POWF_HD inline float spt_glibc_powf(float x, float y)
     const double r = __builtin_fma(z, invc, -1.0);
     const double y0 = logc + (double)k;
     const double r2 = r * r;
-    double yy = __builtin_fma(kLog2Poly[0], r, kLog2Poly[1]);
-    const double p = __builtin_fma(kLog2Poly[2], r, kLog2Poly[3]);
+    double yy = __builtin_fma(kLog2Poly[0], r, SPT_POWF_LIT(kLog2Poly[1]));
+    const double p = __builtin_fma(kLog2Poly[2], r, SPT_POWF_LIT(kLog2Poly[3]));
     const double r4 = r2 * r2;
     double q = __builtin_fma(kLog2Poly[4], r, y0);
     q = __builtin_fma(p, r2, q);
@@ -179,7 +198,7 @@ SPT_POWF_HD inline float spt_glibc_powf(float x, float y)
     const uint64_t ski = ki + sign_bias;
     t += ski << (52 - 5);
     const double s = u2d(t);
-    const double zz = __builtin_fma(kExp2Poly[0], rr, kExp2Poly[1]);
+    const double zz = __builtin_fma(kExp2Poly[0], rr, SPT_POWF_LIT(kExp2Poly[1]));
     const double rr2 = rr * rr;
     double e = __builtin_fma(kExp2Poly[2], rr, 1.0);
     e = __builtin_fma(zz, rr2, e);

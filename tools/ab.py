@@ -81,3 +81,4 @@ for name, _, _ in ctxs:
     v = np.array(res[name])
     print(f"{name:28s} render ms median {np.median(v):8.3f} min {v.min():8.3f}  "
           f"Msamples/s {W*H*SPP/np.median(v)/1e3:9.1f}  identical={same}")
+    print(f"{'':28s} rounds " + " ".join(f"{x:.3f}" for x in v))
