@@ -124,6 +124,28 @@ inline void sync_globals()
         pinned = g_data;
 }
 
+// cd::FindClosestIntersectionSphere (Collision.hpp:87-109) for n rays at once, on the device
+// and the scene of the globals: origins4 / dirs4 are n Vec4s (w ignored), idx[i] the closest
+// sphere of ray i or g_sphereNumber on a miss, exactly as the reference returns it.
+inline void FindClosestIntersectionSpheres(const float *origins4, const float *dirs4, uint32_t n, uint32_t *idx)
+{
+    sync_globals();
+    spt_ctx *ctx = context();
+    check(ctx, spt_cast_rays(ctx, origins4, dirs4, n, idx, nullptr), "spt_cast_rays");
+}
+
+// The sphere under pixel (x, y) -- the one sample 0's primary ray meets first, as the
+// render sees it -- or g_sphereNumber over the sky: picking from the GL preview.
+inline uint32_t PickSphere(uint32_t x, uint32_t y)
+{
+    sync_globals();
+    spt_ctx *ctx = context();
+    const uint32_t xys[3] = {x, y, 0u};
+    uint32_t idx = g_sphereNumber;
+    check(ctx, spt_primary_hits(ctx, xys, 1, &idx, nullptr, nullptr), "spt_primary_hits");
+    return idx;
+}
+
 }  // namespace spt_shim
 
 // SingleThreadPathTracer.hpp:114-137

@@ -380,6 +380,32 @@ SPT_API void spt_tiles_destroy(spt_tiles *t);
 SPT_API int spt_render_samples(spt_ctx *ctx, int mode, uint32_t yBegin, uint32_t yEnd, uint32_t xBegin, uint32_t xEnd,
                        float *out);
 
+/* ---- ray queries: batched FindClosestIntersectionSphere (Collision.hpp:87-109) ---------
+ * The closest sphere of rays the caller chooses, cast with the render's own traversals
+ * of the current culling shape (spt_set_cluster_size / spt_set_cluster_tree; results are
+ * identical for any): picking, object-id / depth / normal buffers, visibility queries.
+ * Rays are float4 {ox, oy, oz, -} and {dx, dy, dz, -}; the w lanes are ignored.
+ * idx[i] = the ORIGINAL index of ray i's closest sphere, or the scene's sphere count on a
+ *   miss (what the reference returns: g_sphereNumber).
+ * hit (nullable): two float4 per ray, {Px, Py, Pz, t} with P = o + d t the closest contact
+ *   point (Collision.hpp:49-56) and {nx, ny, nz, ds} with n = Normalize(P - C) the contact
+ *   normal (67-71) and ds the squared distance the winner was chosen by; eight +0 on a miss.
+ * They need a scene only (spt_primary_hits: camera and params too), use member 0 of a
+ * multi-device context, end a resident render-service session first, and leave spt_stats
+ * untouched.  n == 0 is SPT_OK and touches nothing. */
+/* device pointers, asynchronous on `stream` (NULL = default stream) */
+SPT_API int spt_cast_rays_async(spt_ctx *ctx, const void *d_origins4, const void *d_dirs4, uint32_t n, void *d_idx,
+                                void *d_hit /*nullable*/, void *stream);
+/* host pointers, blocking; staged in chunks (at most 256 MiB of staging, as spt_render_samples) */
+SPT_API int spt_cast_rays(spt_ctx *ctx, const float *origins4, const float *dirs4, uint32_t n, uint32_t *idx,
+                          float *hit /*nullable*/);
+/* (x, y, s) triples -> closest sphere of that sample's primary ray; needs camera and params.
+ * The ray is the render's own: stream keyed by (seed, y * width + x, s), the u draw first,
+ * viewMatrix * (-1 + 2v, -1 + 2u, 1, 0) normalized, from the eye; dirs4 (nullable) receives
+ * the directions (float4, w = 0).  SPT_ERR_ARG for x >= width, y >= height or s >= spp. */
+SPT_API int spt_primary_hits(spt_ctx *ctx, const uint32_t *xys, uint32_t n, uint32_t *idx, float *hit /*nullable*/,
+                             float *dirs4 /*nullable*/);
+
 SPT_API int spt_get_stats(spt_ctx *ctx, spt_stats *out);
 SPT_API int spt_reset_stats(spt_ctx *ctx);
 

@@ -145,6 +145,9 @@ def lib() -> ctypes.CDLL:
         "spt_tiles_destroy": ([P], None),
         "spt_tiles_abort": ([P], I),
         "spt_service_set_full_grid": ([P, u32], I),
+        "spt_cast_rays_async": ([P, P, P, u32, P, P, P], I),
+        "spt_cast_rays": ([P, P, P, u32, P, P], I),
+        "spt_primary_hits": ([P, P, u32, P, P, P], I),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

@@ -548,4 +548,49 @@ uint32_t render_block_size();  // kRenderBlock of the kernel object (the launch 
 // true when launch_render walks this tree lane by lane (LDS or global-memory lane walk)
 bool lane_walk_tree(const AccelView &ac);
 
+// Node counts that choose a tree's walk (launch_render, spt_kernels.hip; launch_cast,
+// spt_cast.hip).
+// 32-byte node records (pad included) of the LDS copy per block: 2432 = 76 KiB, with the
+// sampler's 4 KiB exactly half of the CU's 160 KiB
+#ifndef SPT_LDS_NODES
+#define SPT_LDS_NODES 2432
+#endif
+constexpr uint32_t kLdsNodeRecords = SPT_LDS_NODES;
+// smallest tree walked from LDS: below it the 8 octant layouts (64 nodes: 16 KiB) fit
+// the scalar cache
+#ifndef SPT_LDS_MIN_NODES
+#define SPT_LDS_MIN_NODES 64
+#endif
+constexpr uint32_t kLdsMinNodes = SPT_LDS_MIN_NODES;
+// largest tree walked lane by lane from global memory; larger ones take the wave walk
+// (stress scenes at 16 spp, lane / wave walk: 20 000 spheres, 4 083 nodes, 12.7 / 18.6
+// ms; 30 000, 6 104: 15.6 / 20.1; 40 000, 8 115: 17.7 / 20.2; 50 000, 10 053: 23.8 /
+// 21.2 -- the per-lane node reads outgrow the caches)
+#ifndef SPT_GLANE_MAX_NODES
+#define SPT_GLANE_MAX_NODES 9000
+#endif
+constexpr uint32_t kGlaneMaxNodes = SPT_GLANE_MAX_NODES;
+
+// ---- ray queries (spt_cast.hip; spt_cast_rays[_async], spt_primary_hits) ---------------
+// n rays, one per lane, cast with the render kernels' traversals.  Ray mode: origins o and
+// directions d (float4, w ignored).  Camera mode (xys non-null): (x, y, s) triples, each
+// the primary ray of sample s of pixel (x, y) from the eye, its direction written to
+// dirs (nullable).  idx[i] = the winner's original sphere index, n_spheres on a miss;
+// hit (nullable) = two float4 per ray: {P, t} and {n, ds}, all +0 on a miss.
+struct CastArgs {
+    AccelView accel;
+    uint32_t n_spheres, n;
+    const float4 *o, *d;
+    const uint32_t *xys;
+    Camera cam;
+    uint32_t width, height;
+    uint64_t seed_key;  // fmix64(seed)
+    uint32_t *idx;
+    float4 *hit, *dirs;
+};
+// the kernel launch_cast picks for a traversal shape: launch_render's rule
+enum : uint32_t { kCastWalkFlat4 = 0, kCastWalkFlat8 = 1, kCastWalkWave = 2, kCastWalkLds = 3, kCastWalkGlane = 4 };
+uint32_t cast_walk(const AccelView &ac);
+hipError_t launch_cast(const CastArgs &a, hipStream_t s);
+
 }  // namespace spt

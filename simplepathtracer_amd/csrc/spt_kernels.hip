@@ -58,30 +58,12 @@ namespace spt {
 #define SPT_LDS_BLOCK 1024
 #endif
 constexpr uint32_t kLdsBlock = SPT_LDS_BLOCK;
-// 32-byte node records (pad included) per block: 2432 = 76 KiB, with the sampler's
-// 4 KiB exactly half of the CU's 160 KiB
-#ifndef SPT_LDS_NODES
-#define SPT_LDS_NODES 2432
-#endif
-constexpr uint32_t kLdsNodeRecords = SPT_LDS_NODES;
+// (kLdsNodeRecords, kLdsMinNodes and kGlaneMaxNodes, the node counts that choose the walk,
+// are in spt_internal.h: the cast kernels of spt_cast.hip follow the same rule)
 // the LDS-tree session kernel (render_kernel_svc_lds) also holds its waves' job records
 // (16 x kSvcRecWords words = 80 records' worth): its table is that much shorter, so that
 // two blocks still fit a CU (at 81 920 B the compiler keeps 64 VGPRs, 8 waves per SIMD)
 constexpr uint32_t kLdsSvcNodeRecords = kLdsNodeRecords - 80u;
-// smallest tree walked from LDS: below it the 8 octant layouts (64 nodes: 16 KiB) fit
-// the scalar cache
-#ifndef SPT_LDS_MIN_NODES
-#define SPT_LDS_MIN_NODES 64
-#endif
-constexpr uint32_t kLdsMinNodes = SPT_LDS_MIN_NODES;
-// largest tree walked lane by lane from global memory; larger ones take the wave walk
-// (stress scenes at 16 spp, lane / wave walk: 20 000 spheres, 4 083 nodes, 12.7 / 18.6
-// ms; 30 000, 6 104: 15.6 / 20.1; 40 000, 8 115: 17.7 / 20.2; 50 000, 10 053: 23.8 /
-// 21.2 -- the per-lane node reads outgrow the caches)
-#ifndef SPT_GLANE_MAX_NODES
-#define SPT_GLANE_MAX_NODES 9000
-#endif
-constexpr uint32_t kGlaneMaxNodes = SPT_GLANE_MAX_NODES;
 #ifndef SPT_LANE_BUDGET
 #define SPT_LANE_BUDGET 7
 #endif

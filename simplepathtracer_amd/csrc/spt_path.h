@@ -3,7 +3,8 @@
 // shading step of the flattened recursion, the cooperative cube-minus-ball
 // sampler and the primary-ray generator.  Included by spt_kernels.hip (the
 // persistent megakernel) and spt_wavefront.hip (the queue-based variant), so
-// both compute every path with the same instructions.
+// both compute every path with the same instructions, and by spt_cast.hip (the
+// ray-query kernels), which cast the caller's rays with the same traversals.
 #pragma once
 #include "spt_device.h"
 #include "spt_internal.h"

@@ -208,6 +208,62 @@ class Context:
         self._check(_native.lib().spt_render_task_range_async(self._h, i0, i1, ctypes.c_void_p(d_rgba or None),
                                                               ctypes.c_void_p(stream or None)))
 
+    @staticmethod
+    def _rays4(a, what) -> np.ndarray:
+        a = np.asarray(a, np.float32)
+        if a.ndim != 2 or a.shape[1] not in (3, 4):
+            raise ValueError(f"{what}: expected an (n, 3) or (n, 4) array, got shape {a.shape}")
+        if a.shape[1] == 3:
+            a = np.concatenate([a, np.zeros((len(a), 1), np.float32)], axis=1)
+        return np.ascontiguousarray(a)
+
+    def cast_rays(self, origins, dirs, hits=False):
+        """cd::FindClosestIntersectionSphere (Collision.hpp:87-109) for n rays on the device
+        (spt_cast_rays): origins and dirs are (n, 3) or (n, 4) float arrays (w ignored).
+        Returns idx (uint32: the closest sphere's index, the sphere count on a miss), or with
+        hits=True (idx, hit) where hit[i] = [[Px, Py, Pz, t], [nx, ny, nz, ds]]: contact
+        point and parameter, contact normal and the squared distance compared; zeros on a
+        miss."""
+        o, d = self._rays4(origins, "origins"), self._rays4(dirs, "dirs")
+        if len(o) != len(d):
+            raise ValueError(f"{len(o)} origins for {len(d)} directions")
+        idx = np.zeros(len(o), np.uint32)
+        hit = np.zeros((len(o), 2, 4), np.float32) if hits else None
+        self._check(_native.lib().spt_cast_rays(self._h, _p(o), _p(d), len(o), _p(idx), _p(hit) if hits else None))
+        return (idx, hit) if hits else idx
+
+    def cast_rays_async(self, d_origins, d_dirs, n, d_idx, d_hit=0, stream=0) -> None:
+        """Device-resident cast_rays (spt_cast_rays_async): raw device pointers to n float4
+        origins and directions, n uint32 indices and (optionally) 2 n float4 hit records,
+        enqueued on `stream` (a hipStream_t; 0 = the default stream)."""
+        self._check(_native.lib().spt_cast_rays_async(self._h, ctypes.c_void_p(d_origins or None),
+                                                      ctypes.c_void_p(d_dirs or None), int(n),
+                                                      ctypes.c_void_p(d_idx or None), ctypes.c_void_p(d_hit or None),
+                                                      ctypes.c_void_p(stream or None)))
+
+    def primary_hits(self, xys, hits=False, dirs=False):
+        """The closest sphere of the primary ray of sample s of pixel (x, y), for every
+        (x, y, s) row of xys (spt_primary_hits; the render's own ray).  Returns idx, followed
+        by hit (as cast_rays) with hits=True and by the (n, 4) directions with dirs=True."""
+        t = np.ascontiguousarray(np.asarray(xys, np.uint32).reshape(-1, 3))
+        idx = np.zeros(len(t), np.uint32)
+        hit = np.zeros((len(t), 2, 4), np.float32) if hits else None
+        dv = np.zeros((len(t), 4), np.float32) if dirs else None
+        self._check(_native.lib().spt_primary_hits(self._h, _p(t), len(t), _p(idx), _p(hit) if hits else None,
+                                                   _p(dv) if dirs else None))
+        out = (idx,) + ((hit,) if hits else ()) + ((dv,) if dirs else ())
+        return out if len(out) > 1 else idx
+
+    def id_buffer(self, s: int = 0) -> np.ndarray:
+        """The picking / object-id buffer: an (H, W) uint32 image of the sphere sample s of
+        every pixel sees first (the sphere count where it sees the sky)."""
+        if self._frame is None:
+            raise _native.SptError(2, "params not set (set_params)")
+        w, h = self._frame
+        ys, xs = np.mgrid[0:h, 0:w]
+        xys = np.stack([xs.ravel(), ys.ravel(), np.full(w * h, s)], axis=1).astype(np.uint32)
+        return self.primary_hits(xys).reshape(h, w)
+
     def synchronize(self) -> None:
         self._check(_native.lib().spt_synchronize(self._h))
 
