@@ -2,20 +2,36 @@
 
 TEST INFRASTRUCTURE ONLY: imported by tests/, __graft_entry__.smoke() and
 bench.py's cpu_baseline leg, never by the product package.  See spt_oracle.h for
-the parity status ("parity unpinned" end to end; building blocks pinned by KATs).
+what is pinned against the reference's own code and what is not.
+
+The ref_* functions run the reference's own functions through oracle/_ref/ref_harness
+(`make -C oracle ref`, built where the reference's headers are present), one process and
+one request per call, under a time limit.
 """
 from __future__ import annotations
 
 import ctypes
 import os
+import struct
 import subprocess
+import tempfile
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "build", "libspt_oracle.so")
 
+REF_BIN = os.path.join(HERE, "_ref", "ref_harness")
+# the reference's include/ directory on the build machine (the Makefile's default too)
+REF_INCLUDE = os.environ.get("REF_INCLUDE", "/root/reference/include")
+REF_TIMEOUT = 60.0
+REF_WIDTH = REF_HEIGHT = 1440  # Globals.hpp: constexpr, as are 100 spp and 10 bounces
+REF_SPP, REF_BOUNCES = 100, 10
+
 SKYBOX, REFLECTIVE, REFRACTIVE, DIFFUSE = 0, 1, 2, 3
+# spo_trace_ray's info: [specular events, cut at the cap] + the SPO_EV_* counters
+EV = ("diffuse", "mirror", "glass_reflect", "refract_twice", "tir", "end_bounces", "end_sky", "cut")
+TRACE_INFO = 2 + len(EV)
 
 
 class Scene(ctypes.Structure):
@@ -76,6 +92,12 @@ def lib():
             fn.argtypes = [P, P, u32, u32, u32, u32, P, P]; fn.restype = u64
         L.spo_render_image_parallel.argtypes = [P, P, u32, ctypes.c_int, P, P]
         L.spo_render_image_parallel.restype = ctypes.c_int
+        L.spo_primary_ray.argtypes = [P, u32, u32, P, P]; L.spo_primary_ray.restype = None
+        L.spo_trace_ray.argtypes = [P, P, P, P, u32, P, P, P]; L.spo_trace_ray.restype = u32
+        L.spo_render_segment_stream.argtypes = [P, P, u32, u32, u32, u32, P, P, P]
+        L.spo_render_segment_stream.restype = u64
+        L.spo_render_segment_task_stream.argtypes = [P, P, u32, u32, u32, u32, P, P, P, P]
+        L.spo_render_segment_task_stream.restype = u64
         L.spo_generate_spheres.argtypes = [u32, u32, P, P, P, P, P]; L.spo_generate_spheres.restype = u32
         L.spo_init_spheres.argtypes = [u32, P, P, P, P, P]; L.spo_init_spheres.restype = u32
         _lib = L
@@ -214,3 +236,153 @@ def primary_winners(scene: OracleScene, frame: Frame, xys) -> np.ndarray:
     out = np.zeros(len(xys), np.uint32)
     lib().spo_primary_winners(scene.ref, ctypes.byref(frame), _p(xys), len(xys), _p(out))
     return out
+
+
+def scene_state(seed: int) -> int:
+    """The state a reference thread's generator starts from when its clock reads `seed`."""
+    return int(lib().spo_scene_state(seed & 0xFFFFFFFF))
+
+
+def uniform_draws(seed: int, a: float, b: float, count: int) -> np.ndarray:
+    st = ctypes.c_uint64(scene_state(seed))
+    return np.array([lib().spo_uniform(ctypes.byref(st), a, b) for _ in range(count)], np.float32)
+
+
+def primary_rays(frame: Frame, xy, seed: int) -> np.ndarray:
+    """Directions (n, 4) of one primary ray per (x, y) row, the jitter drawn from one stream
+    that starts at scene_state(seed)."""
+    out = np.zeros((len(xy), 4), np.float32)
+    st = ctypes.c_uint64(scene_state(seed))
+    for i, (x, y) in enumerate(xy):
+        lib().spo_primary_ray(ctypes.byref(frame), int(x), int(y), ctypes.byref(st), out.ctypes.data + 16 * i)
+    return out
+
+
+def trace_rays(scene: OracleScene, frame: Frame, d, o, bounces, seeds):
+    """spo_trace_ray per row: path i starts from (o[i], d[i]) with bounces[i] and draws from
+    the stream scene_state(seeds[i]).  Returns colours (n, 4) and info (n, TRACE_INFO)."""
+    d = np.ascontiguousarray(d, np.float32); o = np.ascontiguousarray(o, np.float32)
+    n = len(d)
+    out = np.zeros((n, 4), np.float32)
+    info = np.zeros((n, TRACE_INFO), np.uint32)
+    fn, sc, fr = lib().spo_trace_ray, scene.ref, ctypes.byref(frame)
+    st = ctypes.c_uint64(0)
+    pst = ctypes.byref(st)
+    for i in range(n):
+        st.value = scene_state(int(seeds[i]))
+        fn(sc, fr, d.ctypes.data + 16 * i, o.ctypes.data + 16 * i, int(bounces[i]), pst, out.ctypes.data + 16 * i,
+           info.ctypes.data + 4 * TRACE_INFO * i)
+    return out, info
+
+
+def render_segment_stream(scene: OracleScene, frame: Frame, yB, yE, xB, xE, seed, task=False):
+    """RenderSegment / RenderSegmentTask on one sequential stream that starts at
+    scene_state(seed).  Returns (rgba of the region, the frame's g_data, samples dropped by
+    the pass cap (task mode; else 0))."""
+    rgba = np.zeros(((yE - yB) * (xE - xB), 4), np.float32)
+    rgb8 = np.zeros(frame.width * frame.height * 3, np.uint8)
+    st = ctypes.c_uint64(scene_state(seed))
+    dropped = ctypes.c_uint64(0)
+    if task:
+        lib().spo_render_segment_task_stream(scene.ref, ctypes.byref(frame), yB, yE, xB, xE, ctypes.byref(st), _p(rgba),
+                                             _p(rgb8), ctypes.byref(dropped))
+    else:
+        lib().spo_render_segment_stream(scene.ref, ctypes.byref(frame), yB, yE, xB, xE, ctypes.byref(st), _p(rgba),
+                                        _p(rgb8))
+    return rgba, rgb8, int(dropped.value)
+
+
+# ---------------------------------------------------------------- the reference's own code
+
+def ref_available() -> bool:
+    return os.path.exists(REF_BIN)
+
+
+def _ref_call(request: bytes) -> bytes:
+    """One request to a fresh ref_harness process; raises on a non-zero exit or the time limit."""
+    with tempfile.TemporaryDirectory(prefix="spt_ref_") as tmp:
+        req, rsp = os.path.join(tmp, "request"), os.path.join(tmp, "response")
+        with open(req, "wb") as f:
+            f.write(request)
+        r = subprocess.run([REF_BIN, req, rsp], capture_output=True, text=True, timeout=REF_TIMEOUT)
+        if r.returncode != 0:
+            raise RuntimeError(f"ref_harness exit {r.returncode}: {r.stderr.strip()}")
+        with open(rsp, "rb") as f:
+            return f.read()
+
+
+def _scene_bytes(scene: OracleScene) -> bytes:
+    c, col = scene.centers.copy(), scene.colors.copy()
+    c[:, 3] = 0
+    col[:, 3] = 0
+    return (struct.pack("<I", scene.s.n) + c.tobytes() + scene.radii.tobytes() + col.tobytes()
+            + scene.materials.tobytes() + scene.fuzz.tobytes())
+
+
+def _scene_from(buf: bytes, at: int = 0):
+    n = struct.unpack_from("<I", buf, at)[0]
+    at += 4
+    def take(dtype, count):
+        nonlocal at
+        a = np.frombuffer(buf, dtype, count, at).copy()
+        at += a.nbytes
+        return a
+    c = take(np.float32, 4 * n).reshape(n, 4); r = take(np.float32, n); col = take(np.float32, 4 * n).reshape(n, 4)
+    m = take(np.uint8, n); fz = take(np.float32, n)
+    return OracleScene(c, r, col, m, fz), at
+
+
+def ref_draws(seed: int, a: float, b: float, count: int) -> np.ndarray:
+    """The first `count` random::GenerateUniformRealDist(a, b) of a fresh thread seeded `seed`."""
+    return np.frombuffer(_ref_call(struct.pack("<IIffI", 1, seed, a, b, count)), np.float32).copy()
+
+
+def ref_generate(seed: int, init: bool = False) -> OracleScene:
+    """GenerateSpheres() (init: InitSpheres()) on a fresh thread seeded `seed`; fuzz = g_diffuses."""
+    sc, _ = _scene_from(_ref_call(struct.pack("<III", 2, int(init), seed)))
+    return sc
+
+
+def ref_camera(eye, look_at, up) -> np.ndarray:
+    """Transpose(CreateCameraBasisMatrix(eye, look_at, up)), 16 floats."""
+    v = np.concatenate([np.asarray(a, np.float32)[:3] for a in (eye, look_at, up)])
+    return np.frombuffer(_ref_call(struct.pack("<I", 3) + v.tobytes()), np.float32).copy()
+
+
+def ref_geometry(scene: OracleScene, o, d, aim):
+    """Per ray: FindClosestIntersectionSphere (uint32); for hits the ten floats
+    ClosestContactPoint (4), its factor t, ContactNormal (4), LengthSquared(o - P) (zeros on
+    a miss); RaySphereIntersection of sphere aim[i] (False where aim[i] < 0)."""
+    o = np.ascontiguousarray(o, np.float32); d = np.ascontiguousarray(d, np.float32)
+    aim = np.ascontiguousarray(aim, np.int32)
+    n = len(o)
+    buf = _ref_call(struct.pack("<I", 4) + _scene_bytes(scene) + struct.pack("<I", n) + o.tobytes() + d.tobytes()
+                    + aim.tobytes())
+    idx = np.frombuffer(buf, np.uint32, n, 0).copy()
+    rec = np.frombuffer(buf, np.float32, 10 * n, 4 * n).reshape(n, 10).copy()
+    rsi = np.frombuffer(buf, np.uint8, n, 44 * n).astype(bool)
+    return idx, rec, rsi
+
+
+def ref_trace(scene: OracleScene, d, o, bounces, seeds) -> np.ndarray:
+    """TraceAndSampleColor(d[i], o[i], bounces[i]), each on a fresh thread seeded seeds[i]:
+    colours (n, 4)."""
+    d = np.ascontiguousarray(d, np.float32); o = np.ascontiguousarray(o, np.float32)
+    n = len(d)
+    rec = np.zeros(n, np.dtype([("d", "<f4", 4), ("o", "<f4", 4), ("b", "<u4"), ("s", "<u4")]))
+    rec["d"], rec["o"], rec["b"], rec["s"] = d, o, bounces, seeds
+    buf = _ref_call(struct.pack("<I", 5) + _scene_bytes(scene) + struct.pack("<I", n) + rec.tobytes())
+    return np.frombuffer(buf, np.float32, 4 * n).reshape(n, 4).copy()
+
+
+def ref_segment(scene: OracleScene, view, eye, yB, yE, xB, xE, seed, task=False):
+    """RenderSegment (task: RenderSegmentTask) of the 1440 x 1440 frame at 100 spp and 10
+    bounces on a fresh thread seeded `seed`.  Returns (indices, colours (k, 4)) as handed to
+    io::WritePixel, in call order, and the whole g_data (zero before the call)."""
+    req = (struct.pack("<I", 6) + _scene_bytes(scene) + np.asarray(view, np.float32).reshape(16).tobytes()
+           + np.asarray(eye, np.float32).reshape(4).tobytes() + struct.pack("<IIIIII", int(task), seed, yB, yE, xB, xE))
+    buf = _ref_call(req)
+    k = struct.unpack_from("<I", buf, 0)[0]
+    taps = np.frombuffer(buf, np.dtype([("index", "<u4"), ("color", "<f4", 4)]), k, 4)
+    g = np.frombuffer(buf, np.uint8, REF_WIDTH * REF_HEIGHT * 3, 4 + 20 * k).copy()
+    return taps["index"].copy(), taps["color"].copy(), g

@@ -261,11 +261,12 @@ void spo_write_pixel(const float c[4], uint8_t out[3]) { write_pixel(out, ld4w(c
 typedef struct tctx {
     const spo_scene *sc;
     const spo_frame *fr;
-    uint64_t st;
+    uint64_t *st; /* the path's stream: a keyed state of the caller's, or a caller's raw stream */
     uint32_t casts;
     uint32_t spec;
     int task_mode;
     int dropped;
+    uint32_t ev[SPO_EV_COUNT]; /* what the path went through (SPO_EV_*) */
 } tctx;
 
 static v4 trace(tctx *t, v4 d, v4 o, uint32_t bounce);
@@ -284,16 +285,18 @@ static v4 sample_diffuse(tctx *t, v4 d, v4 o, uint32_t bounce, uint32_t idx)
 {
     const spo_scene *sc = t->sc;
     v4 color = vmul(ld4(sc->colors + 4 * (size_t)idx), 0.5f);
+    t->ev[SPO_EV_DIFFUSE]++;
     o = closest_contact(center(sc, idx), sc->radii[idx], o, d);
-    d = vnorm(vadd(contact_normal(o, center(sc, idx)), ball_vector(&t->st)));
+    d = vnorm(vadd(contact_normal(o, center(sc, idx)), ball_vector(t->st)));
     idx = cast(t, d, o);
     while (--bounce && idx < sc->n) {
         color = vmul(color, 0.5f);
         o = closest_contact(center(sc, idx), sc->radii[idx], o, d);
         v4 n = contact_normal(o, center(sc, idx));
-        d = vnorm(vadd(vadd(o, n), ball_vector(&t->st)));
+        d = vnorm(vadd(vadd(o, n), ball_vector(t->st)));
         idx = cast(t, d, o);
     }
+    if (!bounce) t->ev[SPO_EV_END_BOUNCES]++;
     return color;
 }
 
@@ -302,7 +305,7 @@ static int specular_event(tctx *t)
 {
     t->spec++;
     if (t->task_mode && t->spec >= SPO_TASK_PASSES) { t->dropped = 1; return 1; }
-    if (t->spec > SPO_SPECULAR_CAP) return 1;
+    if (t->spec > SPO_SPECULAR_CAP) { t->ev[SPO_EV_CUT]++; return 1; }
     return 0;
 }
 
@@ -310,9 +313,10 @@ static int specular_event(tctx *t)
 static v4 sample_reflective(tctx *t, v4 d, v4 o, uint32_t bounce, uint32_t idx)
 {
     const spo_scene *sc = t->sc;
+    t->ev[SPO_EV_MIRROR]++;
     o = closest_contact(center(sc, idx), sc->radii[idx], o, d);
     v4 n = contact_normal(o, center(sc, idx));
-    d = vnorm(vadd(vreflect(d, n), vmul(ball_vector(&t->st), sc->fuzz[idx])));
+    d = vnorm(vadd(vreflect(d, n), vmul(ball_vector(t->st), sc->fuzz[idx])));
     if (specular_event(t)) return V3(0.f, 0.f, 0.f);
     return trace(t, d, o, bounce);
 }
@@ -372,7 +376,8 @@ static v4 sample_refractive(tctx *t, v4 d, v4 o, uint32_t bounce, uint32_t idx)
     float schlick = schlick_of(rsq, c);
     v4 nd;
 
-    if (spo_uniform(&t->st, 0.f, 1.f) < schlick) {
+    if (spo_uniform(t->st, 0.f, 1.f) < schlick) {
+        t->ev[SPO_EV_GLASS_REFLECT]++;
         nd = vreflect(d, n);
     } else if (no_tir(r, c)) {
         d = refract_dir(d, n, r, c);
@@ -382,13 +387,18 @@ static v4 sample_refractive(tctx *t, v4 d, v4 o, uint32_t bounce, uint32_t idx)
         r = nGlass / nAir;
         rsq = powf((nGlass - nAir) / (nGlass + nAir), 2.f);
         schlick = schlick_of(rsq, c);
-        if (spo_uniform(&t->st, 0.f, 1.f) < schlick)
+        if (spo_uniform(t->st, 0.f, 1.f) < schlick) {
+            t->ev[SPO_EV_GLASS_REFLECT]++;
             nd = vreflect(d, n);
-        else if (no_tir(r, c))
+        } else if (no_tir(r, c)) {
+            t->ev[SPO_EV_REFRACT_TWICE]++;
             nd = refract_dir(d, n, r, c);
-        else
+        } else {
+            t->ev[SPO_EV_TIR]++;
             nd = vreflect(d, n);
+        }
     } else {
+        t->ev[SPO_EV_TIR]++;
         nd = vreflect(d, n);
     }
     if (specular_event(t)) return V3(0.f, 0.f, 0.f);
@@ -407,6 +417,7 @@ static v4 trace(tctx *t, v4 d, v4 o, uint32_t bounce)
         default: break;
         }
     }
+    t->ev[SPO_EV_END_SKY]++;
     return sky(t, d);
 }
 
@@ -417,6 +428,12 @@ static inline v4 primary_dir(const spo_frame *fr, uint64_t *st, uint32_t x, uint
     float u = ((float)y + spo_uniform(st, -1.f, 1.f)) / (float)fr->width;
     float v = ((float)x + spo_uniform(st, -1.f, 1.f)) / (float)fr->height;
     return vnorm(vmatvec(fr->view, V3(-1.f + 2.f * v, -1.f + 2.f * u, 1.f)));
+}
+
+/* The primary ray's direction of pixel (x, y), its two jitter draws taken from *state. */
+void spo_primary_ray(const spo_frame *fr, uint32_t x, uint32_t y, uint64_t *state, float d[4])
+{
+    st4(d, primary_dir(fr, state, x, y));
 }
 
 /* The primary ray of sample s of pixel (x, y) (SingleThreadPathTracer.hpp:123-130) and its
@@ -435,8 +452,9 @@ void spo_primary_winners(const spo_scene *sc, const spo_frame *fr, const uint32_
 uint32_t spo_trace_sample(const spo_scene *sc, const spo_frame *fr, uint32_t x, uint32_t y, uint32_t s,
                           int task_mode, float out[4])
 {
-    tctx t = {sc, fr, spo_sample_key(fr->seed, y * fr->width + x, s), 0, 0, task_mode, 0};
-    v4 d = primary_dir(fr, &t.st, x, y);
+    uint64_t key = spo_sample_key(fr->seed, y * fr->width + x, s);
+    tctx t = {sc, fr, &key, 0, 0, task_mode, 0, {0}};
+    v4 d = primary_dir(fr, t.st, x, y);
     v4 c = trace(&t, d, ld4(fr->eye), fr->bounces);
     if (task_mode) c.w = t.dropped ? 0.0f : 1.0f;
     st4(out, c);
@@ -446,13 +464,29 @@ uint32_t spo_trace_sample(const spo_scene *sc, const spo_frame *fr, uint32_t x, 
 uint32_t spo_trace_sample_info(const spo_scene *sc, const spo_frame *fr, uint32_t x, uint32_t y, uint32_t s,
                                int task_mode, float out[4], uint32_t info[2])
 {
-    tctx t = {sc, fr, spo_sample_key(fr->seed, y * fr->width + x, s), 0, 0, task_mode, 0};
-    v4 d = primary_dir(fr, &t.st, x, y);
+    uint64_t key = spo_sample_key(fr->seed, y * fr->width + x, s);
+    tctx t = {sc, fr, &key, 0, 0, task_mode, 0, {0}};
+    v4 d = primary_dir(fr, t.st, x, y);
     v4 c = trace(&t, d, ld4(fr->eye), fr->bounces);
     if (task_mode) c.w = t.dropped ? 0.0f : 1.0f;
     st4(out, c);
     info[0] = t.spec;
     info[1] = (uint32_t)t.dropped;
+    return t.casts;
+}
+
+/* One path of TraceAndSampleColor(d, o, bounces) (SingleThreadPathTracer.hpp:94-112) that
+ * draws from the caller's raw stream *state, as the reference draws from its thread's:
+ * the same trace() as every keyed path above.  fr gives the sky colour only. */
+uint32_t spo_trace_ray(const spo_scene *sc, const spo_frame *fr, const float d[4], const float o[4], uint32_t bounces,
+                       uint64_t *state, float out[4], uint32_t info[SPO_TRACE_INFO])
+{
+    tctx t = {sc, fr, state, 0, 0, 0, 0, {0}};
+    v4 c = trace(&t, ld4w(d), ld4w(o), bounces);
+    st4(out, c);
+    info[0] = t.spec;
+    info[1] = t.ev[SPO_EV_CUT] ? 1u : 0u;
+    for (uint32_t k = 0; k < SPO_EV_COUNT; ++k) info[2 + k] = t.ev[k];
     return t.casts;
 }
 
@@ -463,9 +497,11 @@ static inline size_t g_index(const spo_frame *fr, uint32_t x, uint32_t y)
     return (size_t)(g_size - ((fr->width - x) * 3u + y * fr->width * 3u));
 }
 
-/* SingleThreadPathTracer.hpp:114-137 RenderSegment */
-uint64_t spo_render_segment(const spo_scene *sc, const spo_frame *fr, uint32_t yB, uint32_t yE, uint32_t xB,
-                            uint32_t xE, float *rgba, uint8_t *rgb8)
+/* SingleThreadPathTracer.hpp:114-137 RenderSegment.  stream NULL: every (pixel, sample) draws
+ * from its own keyed state; else every draw of the segment, in the reference's order,
+ * comes from *stream. */
+static uint64_t render_segment(const spo_scene *sc, const spo_frame *fr, uint32_t yB, uint32_t yE, uint32_t xB,
+                               uint32_t xE, float *rgba, uint8_t *rgb8, uint64_t *stream)
 {
     uint64_t casts = 0;
     v4 eye = ld4(fr->eye);
@@ -473,8 +509,9 @@ uint64_t spo_render_segment(const spo_scene *sc, const spo_frame *fr, uint32_t y
         for (uint32_t x = xB; x < xE; ++x) {
             v4 acc = {0.f, 0.f, 0.f, 0.f};
             for (uint32_t s = 0; s < fr->spp; ++s) {
-                tctx t = {sc, fr, spo_sample_key(fr->seed, y * fr->width + x, s), 0, 0, 0, 0};
-                v4 d = primary_dir(fr, &t.st, x, y);
+                uint64_t key = spo_sample_key(fr->seed, y * fr->width + x, s);
+                tctx t = {sc, fr, stream ? stream : &key, 0, 0, 0, 0, {0}};
+                v4 d = primary_dir(fr, t.st, x, y);
                 acc = vadd(acc, trace(&t, d, eye, fr->bounces));
                 casts += t.casts;
             }
@@ -484,6 +521,18 @@ uint64_t spo_render_segment(const spo_scene *sc, const spo_frame *fr, uint32_t y
         }
     }
     return casts;
+}
+
+uint64_t spo_render_segment(const spo_scene *sc, const spo_frame *fr, uint32_t yB, uint32_t yE, uint32_t xB,
+                            uint32_t xE, float *rgba, uint8_t *rgb8)
+{
+    return render_segment(sc, fr, yB, yE, xB, xE, rgba, rgb8, NULL);
+}
+
+uint64_t spo_render_segment_stream(const spo_scene *sc, const spo_frame *fr, uint32_t yB, uint32_t yE, uint32_t xB,
+                                   uint32_t xE, uint64_t *state, float *rgba, uint8_t *rgb8)
+{
+    return render_segment(sc, fr, yB, yE, xB, xE, rgba, rgb8, state);
 }
 
 /* ------------------------------------------------------------------------- */
@@ -528,9 +577,13 @@ static void trace_task(const spo_scene *sc, task_t task, tasks_t *tasks, uint64_
     q_push(&tasks->skybox, task);
 }
 
-/* TaskBasedPathTracer.hpp:54-206 RenderSegmentTask. */
-uint64_t spo_render_segment_task(const spo_scene *sc, const spo_frame *fr, uint32_t yB, uint32_t yE, uint32_t xB,
-                                 uint32_t xE, float *rgba, uint8_t *rgb8)
+/* The stream a task draws from: its own keyed state, or the caller's raw stream. */
+static inline uint64_t *task_stream(task_t *tk, uint64_t *stream) { return stream ? stream : &tk->st; }
+
+/* TaskBasedPathTracer.hpp:54-206 RenderSegmentTask.  stream as in render_segment; dropped, if
+ * not NULL, receives the number of samples the pass cap leaves unresolved. */
+static uint64_t render_segment_task(const spo_scene *sc, const spo_frame *fr, uint32_t yB, uint32_t yE, uint32_t xB,
+                                    uint32_t xE, float *rgba, uint8_t *rgb8, uint64_t *stream, uint64_t *dropped)
 {
     const uint32_t segW = xE - xB, segH = yE - yB;
     /* colorIndex (lines 103, 186) strides rows by segmentHeight; size the arrays so
@@ -554,7 +607,7 @@ uint64_t spo_render_segment_task(const spo_scene *sc, const spo_frame *fr, uint3
                 task_t tk;
                 tk.st = spo_sample_key(fr->seed, y * fr->width + x, s);
                 tk.origin = eye;
-                tk.direction = primary_dir(fr, &tk.st, x, y);
+                tk.direction = primary_dir(fr, task_stream(&tk, stream), x, y);
                 tk.sphere_index = sc->n;
                 tk.bounce_count = fr->bounces;
                 tk.x = x;
@@ -569,14 +622,14 @@ uint64_t spo_render_segment_task(const spo_scene *sc, const spo_frame *fr, uint3
                 uint32_t idx = tk->sphere_index;
                 v4 color = vmul(ld4(sc->colors + 4 * (size_t)idx), 0.5f);
                 tk->origin = closest_contact(center(sc, idx), sc->radii[idx], tk->origin, tk->direction);
-                tk->direction = vnorm(vadd(contact_normal(tk->origin, center(sc, idx)), ball_vector(&tk->st)));
+                tk->direction = vnorm(vadd(contact_normal(tk->origin, center(sc, idx)), ball_vector(task_stream(tk, stream))));
                 casts++;
                 idx = find_closest(sc, tk->direction, tk->origin);
                 while (--tk->bounce_count && idx < sc->n) {
                     color = vmul(color, 0.5f);
                     tk->origin = closest_contact(center(sc, idx), sc->radii[idx], tk->origin, tk->direction);
                     v4 n = contact_normal(tk->origin, center(sc, idx));
-                    tk->direction = vnorm(vadd(vadd(tk->origin, n), ball_vector(&tk->st)));
+                    tk->direction = vnorm(vadd(vadd(tk->origin, n), ball_vector(task_stream(tk, stream))));
                     casts++;
                     idx = find_closest(sc, tk->direction, tk->origin);
                 }
@@ -591,7 +644,7 @@ uint64_t spo_render_segment_task(const spo_scene *sc, const spo_frame *fr, uint3
                 uint32_t idx = tk->sphere_index;
                 tk->origin = closest_contact(center(sc, idx), sc->radii[idx], tk->origin, tk->direction);
                 v4 n = contact_normal(tk->origin, center(sc, idx));
-                tk->direction = vnorm(vadd(vreflect(tk->direction, n), vmul(ball_vector(&tk->st), sc->fuzz[idx])));
+                tk->direction = vnorm(vadd(vreflect(tk->direction, n), vmul(ball_vector(task_stream(tk, stream)), sc->fuzz[idx])));
                 casts++;
                 idx = find_closest(sc, tk->direction, tk->origin);
                 task_t nt = *tk;
@@ -611,7 +664,7 @@ uint64_t spo_render_segment_task(const spo_scene *sc, const spo_frame *fr, uint3
                 float r = nAir / nGlass;
                 float rsq = powf((nAir - nGlass) / (nAir + nGlass), 2.f);
                 float schlick = schlick_of(rsq, c);
-                if (spo_uniform(&tk->st, 0.f, 1.f) < schlick) {
+                if (spo_uniform(task_stream(tk, stream), 0.f, 1.f) < schlick) {
                     tk->direction = vreflect(tk->direction, n);
                 } else if (no_tir(r, c)) {
                     tk->direction = refract_dir(tk->direction, n, r, c);
@@ -621,7 +674,7 @@ uint64_t spo_render_segment_task(const spo_scene *sc, const spo_frame *fr, uint3
                     r = nGlass / nAir;
                     rsq = powf((nGlass - nAir) / (nGlass + nAir), 2.f);
                     schlick = schlick_of(rsq, c);
-                    if (spo_uniform(&tk->st, 0.f, 1.f) < schlick)
+                    if (spo_uniform(task_stream(tk, stream), 0.f, 1.f) < schlick)
                         tk->direction = vreflect(tk->direction, n);
                     else if (no_tir(r, c))
                         tk->direction = refract_dir(tk->direction, n, r, c);
@@ -648,6 +701,7 @@ uint64_t spo_render_segment_task(const spo_scene *sc, const spo_frame *fr, uint3
             swap_tasks(&tasks, &next);
             clear_tasks(&next);
         }
+        if (dropped) *dropped += tasks_size(&tasks);
     }
 
     /* resolve, lines 196-205 */
@@ -663,6 +717,18 @@ uint64_t spo_render_segment_task(const spo_scene *sc, const spo_frame *fr, uint3
     free(colors);
     free(samples);
     return casts;
+}
+
+uint64_t spo_render_segment_task(const spo_scene *sc, const spo_frame *fr, uint32_t yB, uint32_t yE, uint32_t xB,
+                                 uint32_t xE, float *rgba, uint8_t *rgb8)
+{
+    return render_segment_task(sc, fr, yB, yE, xB, xE, rgba, rgb8, NULL, NULL);
+}
+
+uint64_t spo_render_segment_task_stream(const spo_scene *sc, const spo_frame *fr, uint32_t yB, uint32_t yE, uint32_t xB,
+                                        uint32_t xE, uint64_t *state, float *rgba, uint8_t *rgb8, uint64_t *dropped)
+{
+    return render_segment_task(sc, fr, yB, yE, xB, xE, rgba, rgb8, state, dropped);
 }
 
 /* ------------------------------------------------------------------------- */

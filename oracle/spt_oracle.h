@@ -6,12 +6,19 @@
  * __graft_entry__.smoke() and bench.py's cpu_baseline leg may load it, as the
  * checker / CPU timing baseline.
  *
- * PARITY STATUS: the reference (/root/reference, header-only MSVC C++) cannot be
- * built in this image without stand-ins for headers it lacks (<intrin.h>,
- * glbinding/GLFW via Gl.hpp, stb via IOHelpers.hpp), so it is "unbuildable here"
- * and there is no oracle/_ref.  The reference ships no tests or golden vectors.
- * End-to-end pixel values are therefore PARITY UNPINNED against the reference
- * itself.  What IS pinned (tests/test_oracle_kat.py, oracle/kat_*.c*):
+ * PARITY STATUS: the reference (header-only MSVC C++) is built headless behind
+ * stand-ins of our own for the headers it lacks (oracle/ref_standins/: <intrin.h>,
+ * glbinding/GLFW via Gl.hpp, stb via IOHelpers.hpp) by `make ref`, into oracle/_ref/.
+ * tests/test_reference_parity.py compares this file with the reference's own functions
+ * bit for bit: uniform draws from a seeded thread, both scene generators, the camera
+ * basis, FindClosestIntersectionSphere and the contact functions, TraceAndSampleColor
+ * paths (spo_trace_ray) on the golden and the degenerate scenes, RenderSegment and
+ * RenderSegmentTask tiles with g_data (the spo_render_segment*_stream functions, which
+ * share every line with the keyed ones).  NOT pinned: the keyed-stream design below (the
+ * reference can only start a stream at seed << 31 | seed), Renderer.hpp's tiling (needs
+ * GL), MSVC's own code generation and C runtime, more than 255 spheres (the reference
+ * does not terminate), sky colours other than the reference's constant.
+ * Pinned piecewise besides (tests/test_oracle_kat.py, oracle/kat_*.c*):
  *   - uniform draws vs the real libstdc++ std::uniform_real_distribution<float>
  *     driven by the reference's splitmix mixer (Random.hpp:30-36, 86-93);
  *   - Vec4 arithmetic (Dot/LengthSquared/Normalize/Reflect/Mat4*Vec4) vs the real
@@ -45,6 +52,16 @@ enum { SPO_SKYBOX = 0, SPO_REFLECTIVE = 1, SPO_REFRACTIVE = 2, SPO_DIFFUSE = 3 }
 #define SPO_SPECULAR_CAP 1024u
 /* RenderSegmentTask's pass cap, TaskBasedPathTracer.hpp:81 (pass < 10). */
 #define SPO_TASK_PASSES 10u
+
+/* What a path went through, counted by spo_trace_ray: sphere hits by material (a glass hit
+ * counts once per Schlick reflection, once if it refracts in and out, once per total
+ * internal reflection), how the path ended (the diffuse walk ran out of bounces; a ray
+ * left for the sky and took its colour) and whether SPO_SPECULAR_CAP cut it. */
+enum {
+    SPO_EV_DIFFUSE = 0, SPO_EV_MIRROR, SPO_EV_GLASS_REFLECT, SPO_EV_REFRACT_TWICE, SPO_EV_TIR,
+    SPO_EV_END_BOUNCES, SPO_EV_END_SKY, SPO_EV_CUT, SPO_EV_COUNT
+};
+#define SPO_TRACE_INFO (2u + SPO_EV_COUNT)
 
 /* Scene SoA, Globals.hpp:31-37 (g_spheres, g_radii, g_colors, g_materials,
  * g_diffuses, g_sphereNumber).  centers/colors are float4 per sphere; the w lane
@@ -95,6 +112,9 @@ int spo_probe_sphere(const spo_scene *sc, uint32_t i, const float d[4], const fl
 /* One (pixel, sample) path of RenderSegment: out[0..3] = color, returns number
  * of FindClosest calls.  task_mode: apply RenderSegmentTask's pass cap; out[3]
  * becomes 1.0 if the sample is counted, 0.0 if dropped. */
+/* Direction of a primary ray of pixel (x, y) (SingleThreadPathTracer.hpp:125-128); the two
+ * jitter draws come from *state. */
+void spo_primary_ray(const spo_frame *fr, uint32_t x, uint32_t y, uint64_t *state, float d[4]);
 void spo_primary_winners(const spo_scene *sc, const spo_frame *fr, const uint32_t *xys, uint32_t n, uint32_t *winner);
 uint32_t spo_trace_sample(const spo_scene *sc, const spo_frame *fr, uint32_t x, uint32_t y,
                           uint32_t s, int task_mode, float out[4]);
@@ -102,6 +122,13 @@ uint32_t spo_trace_sample(const spo_scene *sc, const spo_frame *fr, uint32_t x, 
  * SPO_SPECULAR_CAP or the pass cap included), info[1] = 1 if task mode dropped it. */
 uint32_t spo_trace_sample_info(const spo_scene *sc, const spo_frame *fr, uint32_t x, uint32_t y,
                                uint32_t s, int task_mode, float out[4], uint32_t info[2]);
+/* TraceAndSampleColor(d, o, bounces) drawing from the caller's raw stream *state (advanced
+ * past the path's draws); the code of every keyed path above.  fr supplies the sky colour
+ * only.  out = the colour's four lanes; info[0] = specular events, info[1] = 1 if the path
+ * was cut at SPO_SPECULAR_CAP (the reference would recurse on), info[2 + e] = count of
+ * SPO_EV_e.  Returns the number of FindClosest calls. */
+uint32_t spo_trace_ray(const spo_scene *sc, const spo_frame *fr, const float d[4], const float o[4],
+                       uint32_t bounces, uint64_t *state, float out[4], uint32_t info[SPO_TRACE_INFO]);
 /* Record the base 1 - c of every Schlick powf(1 - c, 5) traced by the calling thread
  * into buf (NULL stops); returns the count since the previous call (may exceed cap). */
 uint32_t spo_schlick_log(float *buf, uint32_t cap);
@@ -114,6 +141,17 @@ uint64_t spo_render_segment(const spo_scene *sc, const spo_frame *fr, uint32_t y
  * queues, its 10-pass cap and its colorIndex stride (correct for square tiles). */
 uint64_t spo_render_segment_task(const spo_scene *sc, const spo_frame *fr, uint32_t yB, uint32_t yE,
                                  uint32_t xB, uint32_t xE, float *rgba, uint8_t *rgb8);
+/* spo_render_segment / spo_render_segment_task with one sequential stream *state running
+ * through every pixel, sample and path in the reference's order, where the keyed
+ * functions give each (pixel, sample) its own: the same code, only the uint64_t * differs.
+ * This is what the reference computes on one thread whose generator starts at *state
+ * (tests/test_reference_parity.py).  dropped (may be NULL) is increased by the number of
+ * samples the 10-pass cap leaves unresolved. */
+uint64_t spo_render_segment_stream(const spo_scene *sc, const spo_frame *fr, uint32_t yB, uint32_t yE,
+                                   uint32_t xB, uint32_t xE, uint64_t *state, float *rgba, uint8_t *rgb8);
+uint64_t spo_render_segment_task_stream(const spo_scene *sc, const spo_frame *fr, uint32_t yB, uint32_t yE,
+                                        uint32_t xB, uint32_t xE, uint64_t *state, float *rgba, uint8_t *rgb8,
+                                        uint64_t *dropped);
 /* RenderImageParallelMain tiling (Renderer.hpp:257-302) with thread_count tiles
  * per side and at most thread_count tiles in flight.  mode 0 = RenderSegment,
  * 1 = RenderSegmentTask.  rgba is a full-frame float4 buffer (may be NULL). */

@@ -1,8 +1,20 @@
-"""Generate tests/golden/*.npz from the CPU restatement (oracle/).
+"""Generate tests/golden/*.npz.
 
-The reference is unbuildable in this image (see oracle/spt_oracle.h), so these
-vectors freeze the oracle's output: they pin the GPU path and guard the oracle
-against regressions.  Run:  python tests/golden/make_golden.py
+    python tests/golden/make_golden.py
+        scenes.npz and golden.npz from the CPU restatement (oracle/).  These vectors
+        freeze the oracle's output: they pin the GPU path and guard the oracle against
+        regressions.  The oracle itself is pinned against the reference's own code by
+        tests/test_reference_parity.py.
+
+    python tests/golden/make_golden.py --reference-casts
+        reference_casts.npz from the answers of the reference's own code
+        (oracle/_ref/ref_harness, built by `make -C oracle ref` where the reference's
+        headers are present): the oracle takes no part.  It holds data only: 1031 rays of
+        tests/cast_rays.make_rays on the `random` scene of scenes.npz (o, d), and for each
+        the reference's FindClosestIntersectionSphere (idx) and the hit record
+        [[P.x, P.y, P.z, t], [n.x, n.y, n.z, ds]] of ClosestContactPoint, its factor,
+        ContactNormal and LengthSquared(o - P), eight +0 on a miss (hit).
+        tests/test_gpu_cast.py casts these rays on the GPU against it.
 """
 from __future__ import annotations
 
@@ -14,7 +26,11 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 import pyoracle as po  # noqa: E402
+from cast_rays import RAY_SEED, make_rays  # noqa: E402
+
+REFERENCE_CASTS_RAYS = 1031
 
 EYE, LOOK, UP, SKY = [0, 1, -3, 0], [0, 1, 0, 0], [0, 1, 0, 0], [137, 207, 240, 0]
 
@@ -94,5 +110,25 @@ def main():
     print("wrote", os.path.join(HERE, "golden.npz"), {k: v.shape for k, v in out.items()})
 
 
+def reference_casts():
+    if not po.ref_available():
+        sys.exit(f"{po.REF_BIN} is not built: run `make -C oracle ref` where the reference's headers are")
+    gs = np.load(os.path.join(HERE, "scenes.npz"), allow_pickle=False)
+    sc = po.OracleScene(*(gs[f"random_{k}"] for k in ("centers", "radii", "colors", "materials", "fuzz")))
+    o, d, _, _ = make_rays(sc.centers, sc.radii, n=REFERENCE_CASTS_RAYS, seed=RAY_SEED)
+    idx, rec, _ = po.ref_geometry(sc, o, d, np.full(len(o), -1, np.int32))
+    hit = np.zeros((len(o), 2, 4), np.float32)
+    hit[:, 0, :3], hit[:, 0, 3] = rec[:, 0:3], rec[:, 4]
+    hit[:, 1, :3], hit[:, 1, 3] = rec[:, 5:8], rec[:, 9]
+    path = os.path.join(HERE, "reference_casts.npz")
+    np.savez_compressed(path, o=o, d=d, idx=idx, hit=hit)
+    print("wrote", path, os.path.getsize(path), "bytes;", int((idx < sc.s.n).sum()), "hits of", len(o))
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["--reference-casts"]:
+        reference_casts()
+    elif sys.argv[1:]:
+        sys.exit(__doc__)
+    else:
+        main()

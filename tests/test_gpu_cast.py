@@ -33,19 +33,17 @@ The oracle's answers must show the mix is live (hit share, misses, kinds C and D
 side of their thresholds) before any of that counts.
 """
 import ctypes
+import os
 
 import numpy as np
 import pytest
 
 import degenerate_scenes as D
+from cast_rays import N_RAYS, RAY_SEED, make_rays, restate_hits
 from test_gpu_parity import EYE, LOOK, UP, SKY, bits, scene_from, setup
 
 pytestmark = pytest.mark.gpu
 
-N_RAYS = 4099
-RAY_SEED = 20240
-KINDS = "ABCDEFG"
-SHARES = (0.25, 0.20, 0.20, 0.10, 0.15, 0.02, 0.08)
 STRESS_SEED = 2
 # scene -> (cluster size, branching) it is cast on
 RANDOM_SHAPES = ((0, 0), (4, 0), (8, 0), (8, 2), (3, 16), (D.AUTO, D.AUTO))
@@ -71,122 +69,7 @@ def spt():
     return m
 
 
-# ---------------------------------------------------------------- rays
-
-def _unit(rng, n):
-    v = rng.normal(size=(n, 3))
-    return v / np.linalg.norm(v, axis=1, keepdims=True)
-
-
-def _perp(rng, d):
-    """A unit vector perpendicular to each row of d."""
-    e = np.cross(d, _unit(rng, len(d)))
-    return e / np.linalg.norm(e, axis=1, keepdims=True)
-
-
-def make_rays(centers, radii, n=N_RAYS, seed=RAY_SEED):
-    """(o, d, kind, aim): float32 (n, 4) origins and directions (w = 0), the kind's letter
-    per ray, and for kinds C and D the sphere aimed at (else -1).  Built in float64 and
-    rounded: the thresholds of C and D are then straddled to within float32 rounding."""
-    rng = np.random.default_rng(seed)
-    C = np.asarray(centers, np.float64)[:, :3]
-    R = np.asarray(radii, np.float64)
-    counts = [int(round(s * n)) for s in SHARES]
-    counts[0] += n - sum(counts)
-    kind = np.array([k for k, c in zip(KINDS, counts) for _ in range(c)])
-    rng.shuffle(kind)
-    o, d = np.zeros((n, 3)), np.zeros((n, 3))
-    aim = np.full(n, -1, np.int64)
-    big = np.nonzero(R * R > 4e-3)[0]
-    eye = np.asarray(EYE, np.float64)[:3]
-
-    def kind_a(m):
-        j = rng.integers(0, len(R), m)
-        nrm = _unit(rng, m)
-        dd = _unit(rng, m)
-        out = np.sum(dd * nrm, axis=1) > 0
-        dd = np.where(out[:, None], dd, -dd)             # outward hemisphere ...
-        dd = np.where((rng.random(m) < 0.5)[:, None], dd, -dd)  # ... or the inward one
-        return C[j] + R[j, None] * nrm, dd
-
-    def kind_b(m):
-        j = rng.integers(0, len(R), m)
-        u = _unit(rng, m) * np.cbrt(rng.random(m))[:, None]
-        t = C[j] + 1.2 * R[j, None] * u - eye
-        return np.broadcast_to(eye, (m, 3)).copy(), t / np.linalg.norm(t, axis=1, keepdims=True)
-
-    def kind_ab(m):
-        oa, da = kind_a(m)
-        ob, db = kind_b(m)
-        pick = (rng.random(m) < 0.5)[:, None]
-        return np.where(pick, oa, ob), np.where(pick, da, db)
-
-    for k in KINDS:
-        sel = np.nonzero(kind == k)[0]
-        m = len(sel)
-        if k == "A":
-            o[sel], d[sel] = kind_a(m)
-        elif k == "B":
-            o[sel], d[sel] = kind_b(m)
-        elif k == "C":
-            j = big[rng.integers(0, len(big), m)]
-            dd = _unit(rng, m)
-            hh = rng.uniform(0.0, 2e-3, m)
-            b = np.sqrt(R[j] * R[j] - hh)
-            o[sel] = C[j] + b[:, None] * _perp(rng, dd) - rng.uniform(3.0, 30.0, m)[:, None] * dd
-            d[sel], aim[sel] = dd, j
-        elif k == "D":
-            j = big[rng.integers(0, len(big), m)]
-            dd = _unit(rng, m)
-            tc = rng.uniform(0.0, 2e-3, m)
-            b = rng.uniform(0.0, 0.5, m) * R[j]  # hh = r^2 - b^2 >= 3e-3: tc alone decides
-            o[sel] = C[j] + b[:, None] * _perp(rng, dd) - tc[:, None] * dd
-            d[sel], aim[sel] = dd, j
-        elif k == "E":
-            oe, de = kind_ab(m)
-            scale = rng.choice([0.5, 2.0, 1.0 + 3e-6, 1.0 - 3e-6], m)
-            o[sel], d[sel] = oe, de * scale[:, None]
-        elif k == "F":
-            of, df = kind_ab(m)
-            both = np.concatenate([of, df], axis=1)
-            both[np.arange(m), rng.integers(0, 6, m)] = rng.choice([np.nan, np.inf, -np.inf, 0.0], m)
-            o[sel], d[sel] = both[:, :3], both[:, 3:]
-        else:
-            og = np.stack([rng.uniform(-20, 20, m), rng.uniform(40, 80, m), rng.uniform(-20, 20, m)], axis=1)
-            dg = _unit(rng, m)
-            dg[:, 1] = np.abs(dg[:, 1])
-            o[sel], d[sel] = og, dg
-    o4, d4 = np.zeros((n, 4), np.float32), np.zeros((n, 4), np.float32)
-    with np.errstate(all="ignore"):
-        o4[:, :3], d4[:, :3] = o, d
-    return o4, d4, kind, aim
-
-
 # ---------------------------------------------------------------- the oracle's side
-
-def restate_hits(centers, radii, idx, o, d):
-    """t, P, n of ClosestContactPoint / ContactNormal for rays (o, d) that hit sphere idx
-    (Collision.hpp:19-27, 49-56, 67-71): float32 throughout, one numpy
-    operation per reference operation (no operation here can contract), sums in Dot's
-    order (x x' + y y') + z z', sqrt and division correctly rounded."""
-    f = np.float32
-    C, r = np.asarray(centers, f)[idx, :3], np.asarray(radii, f)[idx]
-    o, d = np.asarray(o, f)[:, :3], np.asarray(d, f)[:, :3]
-
-    def dot(a, b):
-        return (a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]) + a[:, 2] * b[:, 2]
-
-    with np.errstate(all="ignore"):
-        rs = C - o
-        tc = dot(rs, d)
-        d2 = dot(rs, rs) - tc * tc
-        t = tc - np.sqrt(r * r - d2)
-        P = o + d * t[:, None]
-        v = P - C
-        n = v / np.sqrt(dot(v, v))[:, None]
-    assert t.dtype == P.dtype == n.dtype == f
-    return t, P, n
-
 
 _oracle_cache = {}
 
@@ -303,6 +186,36 @@ def test_cast_rays_match_the_oracle(spt, oracle, golden_scenes, case):
         stream.synchronize()
         assert np.array_equal(ti.cpu().numpy().view(np.uint32), idx), "async idx"
         assert np.array_equal(bits(th.cpu().numpy()), bits(hit)), "async hit records"
+    finally:
+        ctx.close()
+
+
+# ---------------------------------------------------------------- the reference's own answers
+
+@pytest.mark.parametrize("shape", RANDOM_SHAPES, ids=[_case_id(("random", s)) for s in RANDOM_SHAPES])
+def test_cast_rays_match_the_reference_fixture(spt, golden_scenes, shape):
+    """The oracle out of the chain: tests/golden/reference_casts.npz holds what the
+    reference's own FindClosestIntersectionSphere, ClosestContactPoint and ContactNormal
+    answer on 1031 rays of the mix (make_golden.py --reference-casts; checked on the CPU
+    by tests/test_reference_parity.py); the cast must equal it bit for bit."""
+    f = dict(np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_casts.npz"),
+                     allow_pickle=False))
+    s = scene_from(spt, golden_scenes, "random")
+    ctx = spt.Context(0)
+    try:
+        ctx.set_cluster_size(shape[0])
+        ctx.set_cluster_tree(shape[1])
+        ctx.set_scene(s)
+        idx, hit = ctx.cast_rays(f["o"], f["d"], hits=True)
+        is_hit = f["idx"] < s.n
+        assert is_hit.any() and not is_hit.all()
+        bad = np.nonzero(idx != f["idx"])[0]
+        assert bad.size == 0, f"{bad.size} rays pick another sphere; first ray {bad[0]}: got {idx[bad[0]]}, want {f['idx'][bad[0]]}"
+        g, e = bits(hit).reshape(-1, 8), bits(f["hit"]).reshape(-1, 8)
+        assert not g[~is_hit].any(), "a miss is not eight +0"
+        bad = np.nonzero((g != e).any(axis=1))[0]
+        assert bad.size == 0, (f"{bad.size} hit records differ; first ray {bad[0]}: got {hit.reshape(-1, 8)[bad[0]]!r}, "
+                               f"want {f['hit'].reshape(-1, 8)[bad[0]]!r}")
     finally:
         ctx.close()
 
