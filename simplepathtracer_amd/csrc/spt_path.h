@@ -634,13 +634,189 @@ __device__ __forceinline__ Hit find_closest(const AccelView &ac, const f3 &o, co
         return __builtin_fmaf(__builtin_amdgcn_sqrtf(best), 1.00001f, kn);
     };
     float sbl = near_bound(h.best);
-    // node record q of node j: a scalar load, or a broadcast LDS read
-    // (scalar loads off a 32-bit byte offset: one SGPR-offset s_load_dwordx8, no
-    // 64-bit address arithmetic per node)
-    typedef __attribute__((address_space(4))) const char cchar;
-    auto ldn = [&](uint32_t j, int q) -> uint32_t {
-        return LDSN ? lnodes[8 * j + q] : *(cuint *)((cchar *)nodes + (j << 5) + 4 * q);
+    // n nodes stepped, the last of them with mask mm
+    auto diag_node = [&](uint32_t n, unsigned long long mm, bool leaf) {
+        if (SPT_DIAG) {
+            dg.nodes += n;
+            dg.leaves += (mm != 0ull && leaf) ? 1 : 0;
+            if (leaf) {
+                dg.pairs += (unsigned long long)__popcll(mm);
+                dg.leaves8 += (mm != 0ull && __popcll(mm) <= 8) ? 1 : 0;
+                dg.leaves16 += (mm != 0ull && __popcll(mm) <= 16) ? 1 : 0;
+                dg.live += mm != 0ull ? (unsigned long long)__popcll(live_mask) : 0ull;
+            }
+        }
     };
+    // an entered leaf: test its members for the lanes of mm, refresh the near bound
+    auto enter_leaf = [&](uint32_t leaf_slot, unsigned long long mm) {
+        // few lanes need the leaf: deal its (lane, member) pairs (SPT_LEAF_PAIRS)
+        auto leaf_test = [&](const f3 &lo, const f3 &ld, Hit &lh) {
+            if constexpr (SPT_LEAF_PAIRS && LEAF == 8 && !LDSN) {
+                // One of three tests runs: sel = 1 pairs one member a lane, 2 two members
+                // a lane, 0 every lane every member.  They are three separate `if`s on a
+                // selector the compiler cannot see through (the empty asm), not an
+                // if / else chain, so that each updates the winner in place.  In a chain
+                // the later arms read the winner from before the chain while an earlier
+                // arm's result is live (the arms follow each other in the structurized
+                // code), the two get different registers and every leaf entered pays 6
+                // to 9 v_mov for it.
+                const uint32_t nm = (uint32_t)__popcll(mm);
+                const uint32_t sc = scratch != nullptr ? 3u : 0u;
+                uint32_t sel = __builtin_amdgcn_readfirstlane(sc & (nm <= 8u ? 1u : 0u));
+                if (SPT_LEAF_PAIRS >= 2) sel |= __builtin_amdgcn_readfirstlane(sc & (nm > 8u && nm <= 16u ? 2u : 0u));
+                asm volatile("" : "+s"(sel));
+                if (sel & 1u) test_leaf_pairs<LEAF, 1>(ac, leaf_slot, mm, lo, ld, lh, scratch, dg);
+                if (sel & 2u) test_leaf_pairs<LEAF, 2>(ac, leaf_slot, mm, lo, ld, lh, scratch, dg);
+                if (sel == 0u)
+                    test_leaf<LEAF>(slots, ac.orig, leaf_slot, lo, ld, dot(lo, ld), lh, dg);
+            } else {
+                test_leaf<LEAF>(slots, ac.orig, leaf_slot, lo, ld, dot(lo, ld), lh, dg);
+            }
+        };
+        if (SPT_DUP & 16) {
+            Hit h2 = h;
+            h2.best = opaque_v(h2.best);
+            leaf_test(opaque_v3(o), opaque_v3(d), h2);
+            sink_v(h2.idx);
+            sink_v(h2.best);
+            sink_v(h2.t);
+        }
+        leaf_test(o, d, h);
+        sbl = near_bound(h.best);
+    };
+    // the SPT_DUP & 8 copy of the node test (issue attribution builds)
+    auto dup_node = [&](float lx, float ly, float lz, float hx, float hy, float hz) {
+        const float jx = opaque_v(irx), jy = opaque_v(iry), jz = opaque_v(irz);
+        const float ax2 = __builtin_fmaf(lx, jx, qlx), bx2 = __builtin_fmaf(hx, jx, qhx);
+        const float ay2 = __builtin_fmaf(ly, jy, qly), by2 = __builtin_fmaf(hy, jy, qhy);
+        const float az2 = __builtin_fmaf(lz, jz, qlz), bz2 = __builtin_fmaf(hz, jz, qhz);
+        const float tn2 = max3_raw(__builtin_fminf(ax2, bx2), __builtin_fminf(ay2, by2),
+                                   max_raw(__builtin_fminf(az2, bz2), neta));
+        const float tf2 = min3_raw(__builtin_fmaxf(ax2, bx2), __builtin_fmaxf(ay2, by2),
+                                   min_raw(__builtin_fmaxf(az2, bz2), sbl));
+        const unsigned long long mm2 = __ballot(tn2 <= tf2);
+        asm volatile("" ::"s"(mm2));
+    };
+    if constexpr (!LDSN) {
+        // Scalar records: every node step up to the next entered leaf runs inside one asm
+        // block, because around the leaf tests' divergent branches the compiler turns
+        // this loop's uniform branches into flag registers, s_cselect chains and register
+        // copies (25 SALU and 6 v_mov per step).  A step is the box
+        // test's 17 VALU, in the order of the LDS walk below, and 6 or 7 SALU:
+        //  - the position is the record's byte offset `at`, the end is n_nodes << 5;
+        //  - the record lives in ONE block of eight SGPRs: once the six FMAs have read it,
+        //    skip and slot are copied out and the preorder successor's s_load_dwordx8
+        //    lands in the same registers while the min/max chain runs;
+        //  - s_or_b64 of the pass mask and the never-culling lanes sets SCC: one branch;
+        //  - a leaf's skip target is its successor, so only a culled inner node pays the
+        //    dependent reload (after a wait: scalar loads return out of order, and both
+        //    write the same registers).
+        // The record block is fixed (s[52:59]) because the FMAs name its registers one by
+        // one.  Any block of eight SGPRs at a multiple of four will do; 52 is the block the
+        // compiler itself chose for the read-ahead record in render_kernel<true, 8>, above the kernel-argument and launch registers and inside the render
+        // kernels' 96-SGPR cap.  If a new caller's registers collide with it the
+        // compiler copies around the block (read its listing); move the block by
+        // changing the constraint and the seven names in the strings together.
+        // The compiler never sees the record while a load is in flight: every path
+        // out of the block waits first.  Reading the successor of the last node stays
+        // inside the table (each layout ends with a pad record).
+        // Out: slot = the entered leaf and mm = its lanes, the record at `at` (already
+        // the leaf's successor) loaded; or slot = kNoSlot: the walk is over.
+        typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
+        typedef __attribute__((address_space(4))) const u32x8 cu32x8;
+        const uint32_t end = ac.n_nodes << 5;
+        u32x8 nb = *(cu32x8 *)nodes;
+        uint32_t at = 0;
+        while (at < end) {
+            unsigned long long mm;
+            uint32_t skip, slot;
+#if SPT_DIAG
+            uint32_t nn = 0;  // nodes stepped in this block
+#else
+            const uint32_t nn = 0;
+#endif
+            float ax, bx, ay, by, az, bz, tn;
+#define SPT_BOX_FMAS                                    \
+    "v_fma_f32 %[ax], s52, %[irx], %[qlx]\n\t"          \
+    "v_fma_f32 %[bx], s55, %[irx], %[qhx]\n\t"          \
+    "v_fma_f32 %[ay], s53, %[iry], %[qly]\n\t"          \
+    "v_fma_f32 %[by], s58, %[iry], %[qhy]\n\t"          \
+    "v_fma_f32 %[az], s54, %[irz], %[qlz]\n\t"          \
+    "v_fma_f32 %[bz], s59, %[irz], %[qhz]\n\t"
+#define SPT_BOX_CHAIN                                   \
+    "v_min_f32 %[tn], %[ax], %[bx]\n\t"                 \
+    "v_max_f32 %[ax], %[ax], %[bx]\n\t"                 \
+    "v_min_f32 %[bx], %[ay], %[by]\n\t"                 \
+    "v_max_f32 %[ay], %[ay], %[by]\n\t"                 \
+    "v_min_f32 %[by], %[az], %[bz]\n\t"                 \
+    "v_max_f32 %[az], %[az], %[bz]\n\t"                 \
+    "v_max_f32 %[by], %[by], %[neta]\n\t"               \
+    "v_min_f32 %[az], %[az], %[sbl]\n\t"                \
+    "v_max3_f32 %[tn], %[tn], %[bx], %[by]\n\t"         \
+    "v_min3_f32 %[ax], %[ax], %[ay], %[az]\n\t"         \
+    "v_cmp_le_f32_e64 %[mm], %[tn], %[ax]\n\t"
+            asm volatile("1:\n\t"
+#if SPT_DUP & 8
+                         SPT_BOX_FMAS SPT_BOX_CHAIN
+#endif
+                         SPT_BOX_FMAS
+                         "s_mov_b32 %[skip], s56\n\t"
+                         "s_mov_b32 %[slot], s57\n\t"
+                         "s_load_dwordx8 s[52:59], %[base], %[at] offset:0x20\n\t"
+#if SPT_DIAG
+                         "s_add_u32 %[nn], %[nn], 1\n\t"
+#endif
+                         SPT_BOX_CHAIN
+                         "s_add_u32 %[at], %[at], 32\n\t"
+                         "s_or_b64 %[mm], %[mm], %[nocull]\n\t"
+                         "s_cbranch_scc0 2f\n\t"
+                         "s_cmp_lg_u32 %[slot], -1\n\t"
+                         "s_cbranch_scc1 5f\n"  // entered leaf: out
+                         "3:\n\t"                // on to the successor
+                         "s_cmp_lt_u32 %[at], %[end]\n\t"
+                         "s_waitcnt lgkmcnt(0)\n\t"
+                         "s_cbranch_scc1 1b\n\t"
+                         "s_branch 4f\n"
+                         "2:\n\t"                // culled: a leaf's skip target is its successor
+                         "s_cmp_lg_u32 %[slot], -1\n\t"
+                         "s_cbranch_scc1 3b\n\t"
+                         "s_lshl_b32 %[at], %[skip], 5\n\t"
+                         "s_cmp_lt_u32 %[at], %[end]\n\t"
+                         "s_cbranch_scc0 4f\n\t"
+                         "s_waitcnt lgkmcnt(0)\n\t"
+                         "s_load_dwordx8 s[52:59], %[base], %[at]\n\t"
+                         "s_waitcnt lgkmcnt(0)\n\t"
+                         "s_branch 1b\n"
+                         "4:\n\t"                // past the last node
+                         "s_mov_b32 %[slot], -1\n"
+                         "5:\n\t"
+                         "s_waitcnt lgkmcnt(0)"
+                         : [nb] "+{s[52:59]}"(nb), [at] "+s"(at),
+#if SPT_DIAG
+                           [nn] "+s"(nn),
+#endif
+                           [mm] "=&s"(mm), [skip] "=&s"(skip),
+                           [slot] "=&s"(slot), [tn] "=&v"(tn), [ax] "=&v"(ax), [bx] "=&v"(bx), [ay] "=&v"(ay),
+                           [by] "=&v"(by), [az] "=&v"(az), [bz] "=&v"(bz)
+                         : [base] "s"(nodes), [end] "s"(end), [nocull] "s"(tree_nocull), [irx] "v"(irx),
+                           [iry] "v"(iry), [irz] "v"(irz), [qlx] "v"(qlx), [qly] "v"(qly), [qlz] "v"(qlz),
+                           [qhx] "v"(qhx), [qhy] "v"(qhy), [qhz] "v"(qhz), [neta] "v"(neta), [sbl] "v"(sbl)
+                         : "scc");
+#undef SPT_BOX_FMAS
+#undef SPT_BOX_CHAIN
+            // (the block's scalar results pass for lane-varying without this; no instruction)
+            slot = __builtin_amdgcn_readfirstlane(slot);
+            at = __builtin_amdgcn_readfirstlane(at);
+            mm = (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)mm) |
+                 (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(mm >> 32)) << 32;
+            diag_node(nn, mm, slot != kNoSlot);
+            if (slot == kNoSlot) break;
+            enter_leaf(slot, mm);
+        }
+        return h;
+    }
+    // LDS records (layout 0): broadcast reads
+    auto ldn = [&](uint32_t j, int q) -> uint32_t { return lnodes[8 * j + q]; };
     uint32_t i = 0;
     uint32_t nb[8];
 #pragma unroll
@@ -648,17 +824,17 @@ __device__ __forceinline__ Hit find_closest(const AccelView &ac, const f3 &o, co
     while (i < ac.n_nodes) {
         const float lx = __uint_as_float(nb[0]), ly = __uint_as_float(nb[1]), lz = __uint_as_float(nb[2]);
         const float hx = __uint_as_float(nb[3]), hy = __uint_as_float(nb[6]), hz = __uint_as_float(nb[7]);
-        const uint32_t skip = LDSN ? __builtin_amdgcn_readfirstlane(nb[4]) : nb[4];
-        const uint32_t leaf_slot = LDSN ? __builtin_amdgcn_readfirstlane(nb[5]) : nb[5];
-        // LDS walk: this node's scalars before the successor's reads are issued (a
-        // readfirstlane after them would wait for them: LDS waits are lgkmcnt(0))
-        if (LDSN) asm volatile("" ::"s"(skip), "s"(leaf_slot));
+        const uint32_t skip = __builtin_amdgcn_readfirstlane(nb[4]);
+        const uint32_t leaf_slot = __builtin_amdgcn_readfirstlane(nb[5]);
+        // this node's scalars before the successor's reads are issued (a readfirstlane
+        // after them would wait for them: LDS waits are lgkmcnt(0))
+        asm volatile("" ::"s"(skip), "s"(leaf_slot));
         // speculative prefetch of the preorder successor (prefetching the skip
         // target as well measured 4% slower on config 5)
 #pragma unroll
         for (int q = 0; q < 8; ++q) nb[q] = ldn(i + 1, q);
-        // LDS walk: keep the successor's ds_reads ahead of this node's tests
-        if (LDSN) __builtin_amdgcn_sched_barrier(0);
+        // keep the successor's ds_reads ahead of this node's tests
+        __builtin_amdgcn_sched_barrier(0);
         const float ax = __builtin_fmaf(lx, irx, qlx), bx = __builtin_fmaf(hx, irx, qhx);
         const float ay = __builtin_fmaf(ly, iry, qly), by = __builtin_fmaf(hy, iry, qhy);
         const float az = __builtin_fmaf(lz, irz, qlz), bz = __builtin_fmaf(hz, irz, qhz);
@@ -668,58 +844,16 @@ __device__ __forceinline__ Hit find_closest(const AccelView &ac, const f3 &o, co
                                   min_raw(__builtin_fmaxf(az, bz), sbl));
         // inactive lanes have sbl = -inf, so t_f < t_n: no AND with the live mask
         const unsigned long long mm = __ballot(tn <= tf) | tree_nocull;
-        if (SPT_DUP & 8) {
-            const float jx = opaque_v(irx), jy = opaque_v(iry), jz = opaque_v(irz);
-            const float ax2 = __builtin_fmaf(lx, jx, qlx), bx2 = __builtin_fmaf(hx, jx, qhx);
-            const float ay2 = __builtin_fmaf(ly, jy, qly), by2 = __builtin_fmaf(hy, jy, qhy);
-            const float az2 = __builtin_fmaf(lz, jz, qlz), bz2 = __builtin_fmaf(hz, jz, qhz);
-            const float tn2 = max3_raw(__builtin_fminf(ax2, bx2), __builtin_fminf(ay2, by2),
-                                       max_raw(__builtin_fminf(az2, bz2), neta));
-            const float tf2 = min3_raw(__builtin_fmaxf(ax2, bx2), __builtin_fmaxf(ay2, by2),
-                                       min_raw(__builtin_fmaxf(az2, bz2), sbl));
-            const unsigned long long mm2 = __ballot(tn2 <= tf2);
-            asm volatile("" ::"s"(mm2));
-        }
+        if (SPT_DUP & 8) dup_node(lx, ly, lz, hx, hy, hz);
         const bool leaf = leaf_slot != kNoSlot;
-        if (SPT_DIAG) {
-            dg.nodes += 1;
-            dg.leaves += (mm != 0ull && leaf) ? 1 : 0;
-            if (leaf) {
-                dg.pairs += (unsigned long long)__popcll(mm);
-                dg.leaves8 += (mm != 0ull && __popcll(mm) <= 8) ? 1 : 0;
-                dg.leaves16 += (mm != 0ull && __popcll(mm) <= 16) ? 1 : 0;
-                dg.live += mm != 0ull ? (unsigned long long)__popcll(live_mask) : 0ull;
-            }
-        }
-        // (one branch per outcome -- culled inner node / entered leaf / else -- measured
-        // 2% slower on config 2 and 8% on config 5 than this form)
-        if (mm != 0ull && leaf) {
-            // few lanes need the leaf: deal its (lane, member) pairs (SPT_LEAF_PAIRS)
-            auto leaf_test = [&](const f3 &lo, const f3 &ld, Hit &lh) {
-                bool paired = false;
-                if constexpr (SPT_LEAF_PAIRS && LEAF == 8 && !LDSN) {
-                    const uint32_t nm = (uint32_t)__popcll(mm);
-                    if (scratch && nm <= 8u) {
-                        test_leaf_pairs<LEAF, 1>(ac, leaf_slot, mm, lo, ld, lh, scratch, dg);
-                        paired = true;
-                    } else if (SPT_LEAF_PAIRS >= 2 && scratch && nm <= 16u) {
-                        test_leaf_pairs<LEAF, 2>(ac, leaf_slot, mm, lo, ld, lh, scratch, dg);
-                        paired = true;
-                    }
-                }
-                if (!paired) test_leaf<LEAF>(slots, ac.orig, leaf_slot, lo, ld, dot(lo, ld), lh, dg);
-            };
-            if (SPT_DUP & 16) {
-                Hit h2 = h;
-                h2.best = opaque_v(h2.best);
-                leaf_test(opaque_v3(o), opaque_v3(d), h2);
-                sink_v(h2.idx);
-                sink_v(h2.best);
-                sink_v(h2.t);
-            }
-            leaf_test(o, d, h);
-            sbl = near_bound(h.best);
-        }
+        diag_node(1, mm, leaf);
+        // (Written with one branch per outcome -- culled inner node / entered leaf / else
+        // -- this once measured 2% slower on config 2 and 8% on config 5.  That said
+        // nothing about a loop with few instructions: either form compiles to the same
+        // flag registers, s_cselect chains and register copies, because the uniform
+        // branches are structurized together with the leaf tests' divergent ones.  The
+        // scalar walk above has its branches in asm for that reason.)
+        if (mm != 0ull && leaf) enter_leaf(leaf_slot, mm);
         const uint32_t next = (mm != 0ull && !leaf) ? i + 1 : skip;
         if (next != i + 1) {
 #pragma unroll
