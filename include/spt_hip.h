@@ -406,6 +406,33 @@ SPT_API int spt_cast_rays(spt_ctx *ctx, const float *origins4, const float *dirs
 SPT_API int spt_primary_hits(spt_ctx *ctx, const uint32_t *xys, uint32_t n, uint32_t *idx, float *hit /*nullable*/,
                              float *dirs4 /*nullable*/);
 
+/* ---- path queries: batched TraceAndSampleColor (SingleThreadPathTracer.hpp:94-112) -----
+ * The colour along rays the caller chooses: other camera models, light and irradiance
+ * probes, re-shading a G-buffer's secondary rays, radiance along a picked ray.  Ray i is
+ * TraceAndSampleColor(d[i], o[i], bounces) in SPT_MODE_SEGMENT semantics, through the
+ * render's own casts and shading steps; the w lanes of o and d are ignored.
+ * states[i] is the raw splitmix state of ray i: its draw k mixes states[i] + (k + 1) gamma
+ * (Random.hpp:30-36).  The reference's own stream start is seed << 31 | seed
+ * (Random.hpp:19); the render's stream of a sample after its two jitter draws is
+ * spt_sample_state(seed, y * width + x, s, 2).
+ * rgba[i] = the colour, w = +0; 0 for a path cut at the 1024-event specular cap, as in a
+ *   render.  The sky is the initColor of spt_set_camera.
+ * info (nullable): two words per ray, {casts, specular events | cut at the cap << 31}.
+ * They need scene and camera (not params: the depth is `bounces`, and the scene's sample
+ * codes must fit at that depth as spt_set_params demands for its own, else SPT_ERR_ARG),
+ * use member 0 of a multi-device context, end a resident render-service session first, and
+ * leave spt_stats untouched.  bounces == 0 is SPT_ERR_ARG (spt_set_params); n == 0 is
+ * SPT_OK and touches nothing. */
+/* device pointers, asynchronous on `stream` (NULL = default stream) */
+SPT_API int spt_trace_rays_async(spt_ctx *ctx, const void *d_origins4, const void *d_dirs4, const void *d_states,
+                                 uint32_t n, uint32_t bounces, void *d_rgba, void *d_info /*nullable*/, void *stream);
+/* host pointers, blocking; staged in chunks (at most 256 MiB of staging, as spt_cast_rays) */
+SPT_API int spt_trace_rays(spt_ctx *ctx, const float *origins4, const float *dirs4, const uint64_t *states, uint32_t n,
+                           uint32_t bounces, float *rgba, uint32_t *info /*nullable*/);
+/* host only, no device: the state of the render's keyed stream of (seed, pixel, sample)
+ * after `draws` draws, fmix64(fmix64(seed) ^ (pixel << 32 | sample)) + draws * gamma */
+SPT_API int spt_sample_state(uint64_t seed, uint32_t pixel, uint32_t sample, uint32_t draws, uint64_t *state);
+
 SPT_API int spt_get_stats(spt_ctx *ctx, spt_stats *out);
 SPT_API int spt_reset_stats(spt_ctx *ctx);
 

@@ -148,6 +148,9 @@ def lib() -> ctypes.CDLL:
         "spt_cast_rays_async": ([P, P, P, u32, P, P, P], I),
         "spt_cast_rays": ([P, P, P, u32, P, P], I),
         "spt_primary_hits": ([P, P, u32, P, P, P], I),
+        "spt_trace_rays_async": ([P, P, P, P, u32, u32, P, P, P], I),
+        "spt_trace_rays": ([P, P, P, P, u32, u32, P, P], I),
+        "spt_sample_state": ([u64, u32, u32, u32, P], I),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

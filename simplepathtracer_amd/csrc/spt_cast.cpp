@@ -8,9 +8,6 @@ namespace spt_api {
 
 namespace {
 
-// staging of the blocking forms: at most 256 MiB on the device, as spt_render_samples
-constexpr size_t kCastStagingBytes = (size_t)256 << 20;
-
 spt::CastArgs cast_args(const spt_ctx *ctx)
 {
     spt::CastArgs a{};
@@ -26,21 +23,6 @@ int cast_launch(spt_ctx *ctx, const spt::CastArgs &a, hipStream_t s)
     HIP_TRY(ctx, spt::launch_cast(a, s));
     return SPT_OK;
 }
-
-// One device allocation cut into the chunk's arrays (each a multiple of 16 bytes per ray
-// or rounded up to one).
-struct Staging {
-    char *base = nullptr;
-    ~Staging()
-    {
-        if (base) (void)hipFree(base);
-    }
-};
-
-size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
-
-// rays per chunk at per_ray staging bytes each: whole waves, within the staging bound
-size_t cast_chunk(size_t per_ray) { return std::max<size_t>(64, ((kCastStagingBytes - 64) / per_ray) & ~(size_t)63); }
 
 }  // namespace
 

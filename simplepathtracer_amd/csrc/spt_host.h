@@ -485,6 +485,22 @@ void destroy_batch_set(BatchSet *b);
 int reset_one(spt_ctx *ctx);
 int stats_one(spt_ctx *ctx, spt_stats *out);
 
+// Staging of the blocking ray and path queries (spt_cast.cpp, spt_trace.cpp): at most 256 MiB
+// on the device, as spt_render_samples
+constexpr size_t kCastStagingBytes = (size_t)256 << 20;
+// One device allocation cut into the chunk's arrays (each a multiple of 16 bytes per ray
+// or rounded up to one).
+struct Staging {
+    char *base = nullptr;
+    ~Staging()
+    {
+        if (base) (void)hipFree(base);
+    }
+};
+inline size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
+// rays per chunk at per_ray staging bytes each: whole waves, within the staging bound
+inline size_t cast_chunk(size_t per_ray) { return std::max<size_t>(64, ((kCastStagingBytes - 64) / per_ray) & ~(size_t)63); }
+
 template <class T>
 int ensure(spt_ctx *ctx, T **p, size_t *cap, size_t count)
 {

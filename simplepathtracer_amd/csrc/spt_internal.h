@@ -593,4 +593,21 @@ enum : uint32_t { kCastWalkFlat4 = 0, kCastWalkFlat8 = 1, kCastWalkWave = 2, kCa
 uint32_t cast_walk(const AccelView &ac);
 hipError_t launch_cast(const CastArgs &a, hipStream_t s);
 
+// ---- path queries (spt_trace.hip; spt_trace_rays[_async]) ------------------------------
+// n paths, one per lane: TraceAndSampleColor(d[i], o[i], bounces) in segment semantics,
+// every draw of path i from the raw splitmix state st[i].  The trace kernel leaves path
+// i's sample word in the first word of rgba[i] (shade_step's store); the decode pass that
+// follows it on the stream rebuilds the colour there (decode_sample), w = +0.
+// info (nullable) = two words per path: {casts, specular events | cut at the cap << 31}.
+struct TraceArgs {
+    DeviceScene scene;  // code_jmax: the launch's own, from `bounces`
+    uint32_t n, bounces;
+    const float4 *o, *d;
+    const uint64_t *st;
+    float4 *rgba;
+    uint32_t *info;
+};
+// `f`: the scene's shading table, sky and code divisor (fold_args)
+hipError_t launch_trace(const TraceArgs &a, const FoldArgs &f, hipStream_t s);
+
 }  // namespace spt

@@ -40,6 +40,25 @@ class RenderSegmentData:
     xEnd: int = 0
 
 
+def _fmix64(z: np.ndarray) -> np.ndarray:
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def sample_state(seed, pixel, sample, draws=0):
+    """The state of the render's keyed stream of (seed, pixel = y * width + x, sample) after
+    `draws` draws (2 = past the primary ray's jitter), as trace_rays takes it: what
+    spt_sample_state computes, in numpy.  pixel, sample and draws may be arrays (broadcast
+    together): a uint64 array then, else an int."""
+    px, sm, dr = np.broadcast_arrays(np.asarray(pixel, np.uint32), np.asarray(sample, np.uint32),
+                                     np.asarray(draws, np.uint32))
+    key = _fmix64(np.array([int(seed) & 0xFFFFFFFFFFFFFFFF], np.uint64))
+    word = (px.astype(np.uint64) << np.uint64(32)) | sm.astype(np.uint64)
+    out = _fmix64(np.atleast_1d(key ^ word)) + np.atleast_1d(dr.astype(np.uint64)) * np.uint64(0x9E3779B97F4A7C15)
+    return out.reshape(px.shape) if px.ndim else int(out[0])
+
+
 class Context:
     """One device context (spt_ctx) holding scene, camera and config."""
 
@@ -253,6 +272,37 @@ class Context:
                                                    _p(dv) if dirs else None))
         out = (idx,) + ((hit,) if hits else ()) + ((dv,) if dirs else ())
         return out if len(out) > 1 else idx
+
+    def trace_rays(self, origins, dirs, bounces: int, states=None, seed: int = 0, info=False):
+        """TraceAndSampleColor(d, o, bounces) (SingleThreadPathTracer.hpp:94-112) for n rays on
+        the device (spt_trace_rays): origins and dirs are (n, 3) or (n, 4) float arrays (w
+        ignored), states the raw splitmix state each ray draws from (uint64; None: ray i
+        gets sample_state(seed, i, 0)).  Needs scene and camera (the sky).  Returns the
+        colours (n, 4), w = 0, or with info=True (rgba, info) where info[i] = [casts,
+        specular events | cut at the specular cap << 31]."""
+        o, d = self._rays4(origins, "origins"), self._rays4(dirs, "dirs")
+        if len(o) != len(d):
+            raise ValueError(f"{len(o)} origins for {len(d)} directions")
+        if states is None:
+            st = sample_state(seed, np.arange(len(o), dtype=np.uint32), 0)
+        else:
+            st = np.ascontiguousarray(np.asarray(states, np.uint64).reshape(-1))
+            if len(st) != len(o):
+                raise ValueError(f"{len(st)} states for {len(o)} rays")
+        rgba = np.zeros((len(o), 4), np.float32)
+        inf = np.zeros((len(o), 2), np.uint32) if info else None
+        self._check(_native.lib().spt_trace_rays(self._h, _p(o), _p(d), _p(st), len(o), int(bounces), _p(rgba),
+                                                 _p(inf) if info else None))
+        return (rgba, inf) if info else rgba
+
+    def trace_rays_async(self, d_origins, d_dirs, d_states, n, bounces, d_rgba, d_info=0, stream=0) -> None:
+        """Device-resident trace_rays (spt_trace_rays_async): raw device pointers to n float4
+        origins and directions, n uint64 states, n float4 colours and (optionally) 2 n uint32
+        info words, enqueued on `stream` (a hipStream_t; 0 = the default stream)."""
+        self._check(_native.lib().spt_trace_rays_async(self._h, ctypes.c_void_p(d_origins or None),
+                                                       ctypes.c_void_p(d_dirs or None), ctypes.c_void_p(d_states or None),
+                                                       int(n), int(bounces), ctypes.c_void_p(d_rgba or None),
+                                                       ctypes.c_void_p(d_info or None), ctypes.c_void_p(stream or None)))
 
     def id_buffer(self, s: int = 0) -> np.ndarray:
         """The picking / object-id buffer: an (H, W) uint32 image of the sphere sample s of
