@@ -433,6 +433,45 @@ SPT_API int spt_trace_rays(spt_ctx *ctx, const float *origins4, const float *dir
  * after `draws` draws, fmix64(fmix64(seed) ^ (pixel << 32 | sample)) + draws * gamma */
 SPT_API int spt_sample_state(uint64_t seed, uint32_t pixel, uint32_t sample, uint32_t draws, uint64_t *state);
 
+/* ---- feature buffers: first-hit albedo, coverage, normal, depth and ids of the frame ----
+ * What a denoiser or a compositor takes beside the colour, computed on the device from the
+ * frame's own jittered primary rays.  For pixel (x, y) of the frame of spt_set_params, over
+ * samples s = 0 .. spp - 1 in this order: the ray is the render's own (as spt_primary_hits:
+ * stream keyed by (seed, y * width + x, s), from the eye), its closest sphere and hit record
+ * {t, P, n} are those of spt_cast_rays, and per sample, in fp32 without contraction,
+ *   cov = 1 on a hit, else 0;  nrm = n on a hit, else 0;  dep = t on a hit, else 0;
+ *   alb = colors[i].xyz (raw, without the 0.5 of shading) on a DIFFUSE sphere, (1, 1, 1) on
+ *     a REFLECTIVE or REFRACTIVE one, else -- a miss, or a sphere of any other material
+ *     byte, which the reference's switch sends to the skybox -- the sky term
+ *     (sky_c * (d.y + 1.0f)) * 0.5f per channel.  (cov, nrm and dep are geometric: such a
+ *     sphere still counts as hit.)
+ * Each of the eight sums starts at +0, adds its samples in order and is multiplied by
+ * 1.0f / (float)spp (RenderSegment's pixelColor *= 1 / g_samples).
+ * feat: 8 floats per region-local pixel p (row-major), {alb.r, alb.g, alb.b, cov} then
+ *   {nrm.x, nrm.y, nrm.z, dep}.  The mean hit depth is dep / cov; the mean normal is not
+ *   renormalised.
+ * ids: sample 0's sphere per pixel, as idx of spt_primary_hits (the sphere count on a miss).
+ * They need scene, camera and params (SPT_ERR_STATE otherwise), use member 0 of a
+ * multi-device context, end a resident render-service session first, ignore the engine
+ * setting and leave spt_stats and the sample workspaces untouched.  SPT_ERR_ARG for
+ * yEnd > height, xEnd > width, an inverted range, strip == 0, parts == 0, part >= parts, or
+ * both outputs null; an empty rectangle is SPT_OK and touches nothing.  A call is cut into
+ * launches of at most 2^31 - 1 samples, each whole periods of the row map (strip x parts
+ * rows); SPT_ERR_ARG where strip x (xEnd - xBegin) x spp alone exceeds that.
+ * The kernels read the context's primary-ray candidate lists while they run, as renders
+ * do: the setters that rewrite the lists (spt_set_camera, spt_set_params, spt_set_scene and
+ * the culling setters) wait for every features call in flight on any stream, as they wait
+ * for the context's renders, so the async form may be followed by a setter at once. */
+/* host pointers, blocking; rectangle [yBegin,yEnd) x [xBegin,xEnd); staged in chunks of whole
+ * 8-row bands (at most 256 MiB of staging, as spt_cast_rays) */
+SPT_API int spt_render_features(spt_ctx *ctx, uint32_t yBegin, uint32_t yEnd, uint32_t xBegin, uint32_t xEnd,
+                                float *feat /*nullable*/, uint32_t *ids /*nullable*/);
+/* device pointers, asynchronous on `stream` (NULL = default stream); the row map of
+ * spt_render_rows_async, outputs in local pixel order (spt_rows_count rows) */
+SPT_API int spt_render_features_async(spt_ctx *ctx, uint32_t yBegin, uint32_t yEnd, uint32_t strip, uint32_t parts,
+                                      uint32_t part, uint32_t xBegin, uint32_t xEnd, void *d_feat /*nullable*/,
+                                      void *d_ids /*nullable*/, void *stream);
+
 SPT_API int spt_get_stats(spt_ctx *ctx, spt_stats *out);
 SPT_API int spt_reset_stats(spt_ctx *ctx);
 

@@ -151,6 +151,8 @@ def lib() -> ctypes.CDLL:
         "spt_trace_rays_async": ([P, P, P, P, u32, u32, P, P, P], I),
         "spt_trace_rays": ([P, P, P, P, u32, u32, P, P], I),
         "spt_sample_state": ([u64, u32, u32, u32, P], I),
+        "spt_render_features": ([P, u32, u32, u32, u32, P, P], I),
+        "spt_render_features_async": ([P, u32, u32, u32, u32, u32, u32, u32, P, P, P], I),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

@@ -429,10 +429,41 @@ int rebuild_accel(spt_ctx *ctx)
 }
 
 // Wait for every render launch this context has enqueued (on any stream) -- not for the
-// device: unrelated work of the process (torch kernels, RCCL) keeps running.
+// device: unrelated work of the process (torch kernels, RCCL) keeps running.  The feature
+// kernels (spt_features.hip) read the candidate lists on caller streams as renders do:
+// their calls' events (features_mark) are waited for as well.
 int wait_own_renders(spt_ctx *ctx)
 {
     for (const EventPair &p : ctx->pending_render) HIP_TRY(ctx, hipEventSynchronize(p.b));
+    for (hipEvent_t e : ctx->pending_features) HIP_TRY(ctx, hipEventSynchronize(e));
+    ctx->features_pool.insert(ctx->features_pool.end(), ctx->pending_features.begin(), ctx->pending_features.end());
+    ctx->pending_features.clear();
+    return SPT_OK;
+}
+
+// Record that a features call's launches are in flight on stream s (an event behind them,
+// without timing), for wait_own_renders.  Events of calls that have finished go back to the
+// pool first, so the list holds the calls in flight only.
+int features_mark(spt_ctx *ctx, hipStream_t s)
+{
+    std::vector<hipEvent_t> keep;
+    for (hipEvent_t e : ctx->pending_features) {
+        if (hipEventQuery(e) == hipErrorNotReady)
+            keep.push_back(e);
+        else
+            ctx->features_pool.push_back(e);  // done (an error shows at the caller's own synchronisation)
+    }
+    ctx->pending_features.swap(keep);
+    hipEvent_t e = nullptr;
+    if (!ctx->features_pool.empty()) {
+        e = ctx->features_pool.back();
+        ctx->features_pool.pop_back();
+    } else {
+        HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    // in the list before the record: a failed record leaves an event that reads as done
+    ctx->pending_features.push_back(e);
+    HIP_TRY(ctx, hipEventRecord(e, s));
     return SPT_OK;
 }
 
@@ -856,6 +887,8 @@ void spt_ctx_destroy(spt_ctx *ctx)
             (void)hipEventDestroy(p.b);
         }
     (void)hipDeviceSynchronize();  // async renders on caller streams
+    for (auto *vec : {&ctx->pending_features, &ctx->features_pool})
+        for (hipEvent_t e : *vec) (void)hipEventDestroy(e);
     for (const spt_ctx::Pinned &p : ctx->pinned)
         if (p.owner) (void)hipHostUnregister(p.ptr);
     if (ctx->ref_ev) (void)hipEventDestroy(ctx->ref_ev);

@@ -382,6 +382,11 @@ struct spt_ctx {
 
     // timing
     std::vector<EventPair> pending_render, pending_fold, pool;
+    // one event per spt_render_features[_async] call, recorded behind its launches on the
+    // call's stream: those kernels read the primary-ray candidate lists as renders do, so
+    // wait_own_renders waits for them too.  A list of its own: collect_timings and
+    // spt_stats never see it (features_mark, spt_ctx.cpp)
+    std::vector<hipEvent_t> pending_features, features_pool;
     double render_ms = 0, fold_ms = 0, last_render_ms = 0;
     // render-launch intervals relative to ref_ev (recorded before the first launch
     // after a stats reset), for the union of overlapping launches (render_busy_ms)
@@ -432,6 +437,7 @@ uint32_t even_strip(uint32_t height, uint32_t parts);
 int check_not_in_callback(spt_ctx *ctx);
 int rebuild_prim(spt_ctx *ctx);
 int wait_own_renders(spt_ctx *ctx);
+int features_mark(spt_ctx *ctx, hipStream_t s);
 int rebuild_accel(spt_ctx *ctx);
 int ensure_wavefront(spt_ctx *ctx, Workspace *w, uint32_t cap, uint32_t qcap);
 hipStream_t companion_for(spt_ctx *ctx, hipStream_t s);

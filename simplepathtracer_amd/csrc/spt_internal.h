@@ -610,4 +610,25 @@ struct TraceArgs {
 // `f`: the scene's shading table, sky and code divisor (fold_args)
 hipError_t launch_trace(const TraceArgs &a, const FoldArgs &f, hipStream_t s);
 
+// ---- feature buffers (spt_features.hip; spt_render_features[_async]) -------------------
+// Per pixel of the region of RenderArgs::map, over the frame's own primary rays of samples
+// 0 .. spp - 1 in order: feat (nullable) = two float4 per region-local pixel p (row-major),
+// {albedo.rgb, coverage} and {normal.xyz, depth}, each the in-order sum of the per-sample
+// values times 1.0f / (float)spp; ids (nullable) = sample 0's original sphere index, the
+// sphere count on a miss.  The RenderArgs describes a render launch of all spp samples of
+// the region at once; the kernels read of it what start_path_kernarg and prim_list_cast
+// read (map, width, height, bounces, npix, n_items, spp_batch = spp, s0 = 0, seed_key,
+// cam.view, cam.eye, div_band = FastDiv(8 * map.width * spp) where rows >= 8, div_tile =
+// FastDiv(64 * spp), div_strip = FastDiv(map.strip), prim) and scene (accel, mat, shade,
+// n), cam.sky.
+struct FeatArgs {
+    float4 *feat;
+    uint32_t *ids;
+    uint32_t rows;     // rows_owned(map)
+    uint32_t tiles_x;  // 8x8 tiles per band: ceil(map.width / 8)
+    uint32_t tiles;    // ceil(rows / 8) * tiles_x
+    uint32_t spp;
+};
+hipError_t launch_features(const RenderArgs &k, const FeatArgs &f, hipStream_t s);
+
 }  // namespace spt

@@ -314,6 +314,38 @@ class Context:
         xys = np.stack([xs.ravel(), ys.ravel(), np.full(w * h, s)], axis=1).astype(np.uint32)
         return self.primary_hits(xys).reshape(h, w)
 
+    def render_features(self, yB, yE, xB, xE, ids=False):
+        """Feature buffers of the rectangle [yB, yE) x [xB, xE) over the frame's own primary rays
+        (spt_render_features): feat of shape (pixels, 2, 4), float32, per region-local pixel
+        [[albedo r, g, b, coverage], [normal x, y, z, depth]], each the mean over the spp
+        samples (the mean hit depth is depth / coverage); with ids=True (feat, ids), ids the
+        sphere sample 0 sees first (uint32, the sphere count for the sky)."""
+        n = max(yE - yB, 0) * max(xE - xB, 0)
+        feat = np.zeros((n, 2, 4), np.float32)
+        idx = np.zeros(n, np.uint32) if ids else None
+        self._check(_native.lib().spt_render_features(self._h, yB, yE, xB, xE, _p(feat), _p(idx) if ids else None))
+        return (feat, idx) if ids else feat
+
+    def render_features_async(self, yB, yE, strip, parts, part, xB, xE, d_feat=0, d_ids=0, stream=0) -> None:
+        """Device-resident render_features (spt_render_features_async) over the rows of
+        render_rows_async's row map: raw device pointers to 8 floats and / or one uint32 per
+        local pixel, enqueued on `stream` (a hipStream_t; 0 = the default stream)."""
+        self._check(_native.lib().spt_render_features_async(self._h, yB, yE, strip, parts, part, xB, xE,
+                                                            ctypes.c_void_p(d_feat or None),
+                                                            ctypes.c_void_p(d_ids or None),
+                                                            ctypes.c_void_p(stream or None)))
+
+    def feature_buffers(self) -> dict:
+        """The whole frame's feature buffers: albedo (H, W, 3), coverage (H, W), normal
+        (H, W, 3), depth (H, W), all float32, and ids (H, W), uint32."""
+        if self._frame is None:
+            raise _native.SptError(2, "params not set (set_params)")
+        w, h = self._frame
+        feat, idx = self.render_features(0, h, 0, w, ids=True)
+        feat = feat.reshape(h, w, 2, 4)
+        return {"albedo": feat[:, :, 0, :3], "coverage": feat[:, :, 0, 3], "normal": feat[:, :, 1, :3],
+                "depth": feat[:, :, 1, 3], "ids": idx.reshape(h, w)}
+
     def synchronize(self) -> None:
         self._check(_native.lib().spt_synchronize(self._h))
 
