@@ -472,6 +472,56 @@ SPT_API int spt_render_features_async(spt_ctx *ctx, uint32_t yBegin, uint32_t yE
                                       uint32_t part, uint32_t xBegin, uint32_t xEnd, void *d_feat /*nullable*/,
                                       void *d_ids /*nullable*/, void *stream);
 
+/* ---- denoiser: edge-avoiding a-trous filter guided by the feature buffers ---------------
+ * An image-space filter for previews at a few samples per pixel (Dammertz et al. 2010, with
+ * the Lorentzian edge-stopping weight 1 / (1 + x) in place of exp(-x): one division, no
+ * transcendental, so every bit is defined).  It needs no scene, camera or params.
+ * The image is width x height pixels, row-major, p = y * width + x; its borders are the
+ * image's borders, whether it is a frame or a region rendered on its own.
+ *   rgba  float4 per pixel, colours on the 0..255 scale of the renders; w passes through.
+ *   feat  8 floats per pixel as spt_render_features writes them: {alb.r, alb.g, alb.b, cov},
+ *         {nrm.x, nrm.y, nrm.z, dep}.
+ * Everything is fp32, one rounding per operation written, no contraction, IEEE division.
+ * Once: k_t = 1.0f / (sigma_t * sigma_t) for t in {color, albedo, normal, depth}.
+ * Per pixel: z = dep / cov if cov > 0, else +0;  a = alb.rgb and n = nrm.xyz as given.
+ * Level k = 0 .. levels - 1: step s = 2^k, kc_k = k_color * 4^k (exact); the level reads u
+ * (rgba.rgb for k = 0, then the previous level's output) and writes u'.  For pixel p =
+ * (x, y): acc = (+0, +0, +0), ws = +0; then for j = -2 .. 2 (outer), i = -2 .. 2 (inner), the
+ * tap q = (x + i * s, y + j * s), skipped if outside [0, width) x [0, height), else
+ *   du = u_q - u_p;  dc  = (du.r*du.r + du.g*du.g) + du.b*du.b
+ *   da = a_q - a_p;  d_a = (da.r*da.r + da.g*da.g) + da.b*da.b
+ *   dn = n_q - n_p;  d_n = (dn.x*dn.x + dn.y*dn.y) + dn.z*dn.z
+ *   dz = z_q - z_p;  d_z = dz*dz
+ *   X  = (dc*kc_k + d_a*k_albedo) + (d_n*k_normal + d_z*k_depth)
+ *   w  = (h[|i|] * h[|j|]) / (1.0f + X),  h = {0.375f, 0.25f, 0.0625f}
+ *   if !(w > 0) skip the tap (NaN and 0 both skip)
+ *   acc.c = acc.c + w * u_q.c (c = r, g, b);  ws = ws + w
+ * u'_p.c = acc.c / ws if ws > 0, else u'_p = u_p.  The output is the last level's u' and
+ * rgba_p.w.  A pixel with a non-finite colour or feature passes through unchanged and is
+ * skipped by its neighbours, so non-finite values never spread.
+ * out_rgb8 (nullable): the output as a g_data frame of its own width x height, pixel (x, y)
+ * at 3 * ((height - 1 - y) * width + x), each channel io::WritePixel's byte of the output.
+ * Each sigma must be > 0; +inf switches its term off.  levels is 1..8.
+ * Scratch: the caller's, so calls on different streams share no state:
+ * spt_denoise_scratch_bytes gives min(levels - 1, 2) float4 planes of width x height (the
+ * ping-pong between levels; 0 for one level), host only, no device.
+ * They use member 0 of a multi-device context, end a resident render-service session first
+ * and leave spt_stats and the sample workspaces untouched.  SPT_ERR_ARG, before anything is
+ * launched and with the outputs untouched, for a null context or input, both outputs null,
+ * levels outside 1..8, a sigma that is NaN or <= 0, width x height >= 2^31, a null scratch
+ * where spt_denoise_scratch_bytes is not 0, or an output that overlaps rgba, feat or the
+ * scratch.  width == 0 or height == 0 is SPT_OK and touches nothing. */
+SPT_API int spt_denoise_scratch_bytes(uint32_t width, uint32_t height, uint32_t levels, uint64_t *bytes);
+/* device pointers, asynchronous on `stream` (NULL = default stream) */
+SPT_API int spt_denoise_async(spt_ctx *ctx, uint32_t width, uint32_t height, const void *d_rgba, const void *d_feat,
+                              float sigma_color, float sigma_albedo, float sigma_normal, float sigma_depth,
+                              uint32_t levels, void *d_out_rgba /*nullable*/, void *d_out_rgb8 /*nullable*/,
+                              void *d_scratch, void *stream);
+/* host pointers, blocking; allocates and frees its own device buffers */
+SPT_API int spt_denoise(spt_ctx *ctx, uint32_t width, uint32_t height, const float *rgba, const float *feat,
+                        float sigma_color, float sigma_albedo, float sigma_normal, float sigma_depth,
+                        uint32_t levels, float *out_rgba /*nullable*/, uint8_t *out_rgb8 /*nullable*/);
+
 SPT_API int spt_get_stats(spt_ctx *ctx, spt_stats *out);
 SPT_API int spt_reset_stats(spt_ctx *ctx);
 

@@ -89,7 +89,7 @@ def lib() -> ctypes.CDLL:
                           " (no CPU fallback exists)")
     L = ctypes.CDLL(LIB_PATH)
     P, I = ctypes.c_void_p, ctypes.c_int
-    u32, u64 = ctypes.c_uint32, ctypes.c_uint64
+    u32, u64, f32 = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_float
     sig = {
         "spt_abi_version": ([], I),
         "spt_device_count": ([P], I),
@@ -153,6 +153,9 @@ def lib() -> ctypes.CDLL:
         "spt_sample_state": ([u64, u32, u32, u32, P], I),
         "spt_render_features": ([P, u32, u32, u32, u32, P, P], I),
         "spt_render_features_async": ([P, u32, u32, u32, u32, u32, u32, u32, P, P, P], I),
+        "spt_denoise_scratch_bytes": ([u32, u32, u32, P], I),
+        "spt_denoise_async": ([P, u32, u32, P, P, f32, f32, f32, f32, u32, P, P, P, P], I),
+        "spt_denoise": ([P, u32, u32, P, P, f32, f32, f32, f32, u32, P, P], I),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

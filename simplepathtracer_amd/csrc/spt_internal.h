@@ -631,4 +631,21 @@ struct FeatArgs {
 };
 hipError_t launch_features(const RenderArgs &k, const FeatArgs &f, hipStream_t s);
 
+// ---- denoiser (spt_denoise.hip; spt_denoise[_async]) -----------------------------------
+// One level of the a-trous filter over a width x height image: reads `in` (level 0: the
+// caller's rgba, then the previous level's output) and feat, writes out (nullable) and / or
+// the g_data bytes rgb8 (nullable, last level only).  The four factors are 1 / sigma^2, kc
+// already times 4^level.
+struct DenoiseArgs {
+    const float4 *in, *feat;
+    float4 *out;
+    uint8_t *rgb8;
+    uint32_t width, height;
+    uint32_t step;              // 2^level
+    uint32_t sx, sy;            // lattices with a pixel: min(step, width), min(step, height)
+    uint32_t tiles_x, tiles_y;  // 16x16 tiles of the longest lattice: ceil(ceil(width / step) / 16), ...
+    float kc, ka, kn, kz;
+};
+hipError_t launch_denoise_level(const DenoiseArgs &a, hipStream_t s);
+
 }  // namespace spt

@@ -346,6 +346,59 @@ class Context:
         return {"albedo": feat[:, :, 0, :3], "coverage": feat[:, :, 0, 3], "normal": feat[:, :, 1, :3],
                 "depth": feat[:, :, 1, 3], "ids": idx.reshape(h, w)}
 
+    def denoise(self, rgba, feat, sigma_color=30.0, sigma_albedo=0.1, sigma_normal=0.25, sigma_depth=0.5, levels=3,
+                g_data=False):
+        """The edge-avoiding a-trous filter of include/spt_hip.h "denoiser" on the device
+        (spt_denoise).  rgba: an (H, W, 4) float array, colours on the renders' 0..255 scale,
+        or the current frame as (W * H, 4) (what render_frame returns).  feat: what
+        render_features returns for the same pixels ((pixels, 2, 4), or any shape of 8 floats
+        per pixel), or the dict of feature_buffers().  Each sigma must be > 0 (inf switches
+        its term off); levels is 1..8.  Returns the filtered image in rgba's shape, or with
+        g_data=True (image, bytes): bytes the image as a g_data frame of its own W x H."""
+        rgba = np.ascontiguousarray(rgba, np.float32)
+        if rgba.ndim == 3 and rgba.shape[2] == 4:
+            h, w = rgba.shape[:2]
+        elif rgba.ndim == 2 and rgba.shape[1] == 4 and self._frame is not None and \
+                rgba.shape[0] == self._frame[0] * self._frame[1]:
+            w, h = self._frame
+        else:
+            raise ValueError(f"rgba: expected (H, W, 4), or (W * H, 4) of the current frame, got shape {rgba.shape}")
+        if isinstance(feat, dict):
+            feat = np.concatenate([np.asarray(feat["albedo"], np.float32).reshape(h, w, 3),
+                                   np.asarray(feat["coverage"], np.float32).reshape(h, w, 1),
+                                   np.asarray(feat["normal"], np.float32).reshape(h, w, 3),
+                                   np.asarray(feat["depth"], np.float32).reshape(h, w, 1)], axis=2)
+        feat = np.ascontiguousarray(feat, np.float32)
+        if feat.size != w * h * 8:
+            raise ValueError(f"feat: expected 8 floats for each of {w} x {h} pixels, got shape {feat.shape}")
+        out = np.zeros_like(rgba)
+        g = np.zeros(w * h * 3, np.uint8) if g_data else None
+        self._check(_native.lib().spt_denoise(self._h, w, h, _p(rgba), _p(feat), sigma_color, sigma_albedo, sigma_normal,
+                                              sigma_depth, int(levels), _p(out), _p(g) if g_data else None))
+        return (out, g) if g_data else out
+
+    def denoise_async(self, width, height, d_rgba, d_feat, sigma_color=30.0, sigma_albedo=0.1, sigma_normal=0.25,
+                      sigma_depth=0.5, levels=3, d_out=0, d_rgb8=0, d_scratch=0, stream=0) -> None:
+        """Device-resident denoise (spt_denoise_async): raw device pointers to width * height
+        float4 colours, 8 floats of features per pixel, the float4 output and / or the
+        width * height * 3 g_data bytes, and denoise_scratch_bytes(width, height, levels) bytes
+        of scratch of the call's own; one launch per level on `stream` (a hipStream_t; 0 = the
+        default stream)."""
+        self._check(_native.lib().spt_denoise_async(self._h, int(width), int(height), ctypes.c_void_p(d_rgba or None),
+                                                    ctypes.c_void_p(d_feat or None), sigma_color, sigma_albedo,
+                                                    sigma_normal, sigma_depth, int(levels),
+                                                    ctypes.c_void_p(d_out or None), ctypes.c_void_p(d_rgb8 or None),
+                                                    ctypes.c_void_p(d_scratch or None), ctypes.c_void_p(stream or None)))
+
+    def render_denoised(self, **sigmas) -> np.ndarray:
+        """The current frame rendered, its feature buffers, and the frame filtered by denoise
+        (whose keyword arguments `sigmas` takes): render_frame + feature_buffers + denoise.
+        Returns the (H, W, 4) float image, or what denoise returns with g_data=True."""
+        if self._frame is None:
+            raise _native.SptError(2, "params not set (set_params)")
+        w, h = self._frame
+        return self.denoise(self.render_frame().reshape(h, w, 4), self.feature_buffers(), **sigmas)
+
     def synchronize(self) -> None:
         self._check(_native.lib().spt_synchronize(self._h))
 
@@ -386,6 +439,13 @@ def task_range(width, height, parts, part) -> tuple[int, int]:
     a, b = ctypes.c_uint32(), ctypes.c_uint32()
     _native.check(_native.lib().spt_task_range(width, height, parts, part, ctypes.byref(a), ctypes.byref(b)))
     return a.value, b.value
+
+
+def denoise_scratch_bytes(width, height, levels) -> int:
+    """Bytes of scratch a denoise_async call of this shape needs (spt_denoise_scratch_bytes)."""
+    b = ctypes.c_uint64(0)
+    _native.check(_native.lib().spt_denoise_scratch_bytes(int(width), int(height), int(levels), ctypes.byref(b)))
+    return b.value
 
 
 def rows_count(yB, yE, strip, parts, part) -> int:
