@@ -56,25 +56,18 @@ int spt_cast_rays(spt_ctx *ctx, const float *origins4, const float *dirs4, uint3
     if (n == 0) return SPT_OK;
     if (!origins4 || !dirs4 || !idx) return fail(ctx, SPT_ERR_ARG, "null origins, directions or idx");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // per ray: origin + direction in, index (+ two float4) out
-    const size_t per_ray = 2 * sizeof(float4) + sizeof(uint32_t) + (hit ? 2 * sizeof(float4) : 0);
-    const size_t chunk = std::min<size_t>(n, cast_chunk(per_ray));
+    const hipStream_t s = ctx->stream;
     Staging st;
-    const size_t b_vec = chunk * sizeof(float4), b_idx = round16(chunk * sizeof(uint32_t));
-    const size_t bytes = 2 * b_vec + b_idx + (hit ? 2 * b_vec : 0);
-    if (hipMalloc((void **)&st.base, bytes) != hipSuccess) {
-        st.base = nullptr;
-        return fail(ctx, SPT_ERR_NOMEM, "spt_cast_rays: %zu bytes of staging", bytes);
-    }
-    float4 *d_o = (float4 *)st.base, *d_d = (float4 *)(st.base + b_vec);
-    uint32_t *d_idx = (uint32_t *)(st.base + 2 * b_vec);
-    float4 *d_hit = hit ? (float4 *)(st.base + 2 * b_vec + b_idx) : nullptr;
+    if (!st.alloc(cast_rays_plan(n, hit != nullptr), s))
+        return fail(ctx, SPT_ERR_NOMEM, "spt_cast_rays: %zu bytes of staging", st.plan.total);
+    float4 *d_o = st.at<float4>(0), *d_d = st.at<float4>(1), *d_hit = st.at<float4>(3);
+    uint32_t *d_idx = st.at<uint32_t>(2);
     spt::CastArgs a = cast_args(ctx);
     a.o = d_o;
     a.d = d_d;
     a.idx = d_idx;
     a.hit = d_hit;
-    const hipStream_t s = ctx->stream;
+    const size_t chunk = st.plan.chunk;
     for (size_t r0 = 0; r0 < n; r0 += chunk) {
         const size_t m = std::min(chunk, (size_t)n - r0);
         HIP_TRY(ctx, hipMemcpyAsync(d_o, origins4 + 4 * r0, m * sizeof(float4), hipMemcpyHostToDevice, s));
@@ -85,7 +78,7 @@ int spt_cast_rays(spt_ctx *ctx, const float *origins4, const float *dirs4, uint3
         if (hit) HIP_TRY(ctx, hipMemcpyAsync(hit + 8 * r0, d_hit, m * 2 * sizeof(float4), hipMemcpyDeviceToHost, s));
         HIP_TRY(ctx, hipStreamSynchronize(s));
     }
-    return SPT_OK;
+    return st.done(SPT_OK);
 }
 
 int spt_primary_hits(spt_ctx *ctx, const uint32_t *xys, uint32_t n, uint32_t *idx, float *hit, float *dirs4)
@@ -102,20 +95,12 @@ int spt_primary_hits(spt_ctx *ctx, const uint32_t *xys, uint32_t n, uint32_t *id
             return fail(ctx, SPT_ERR_ARG, "triple %zu (x %u, y %u, s %u) outside the %u x %u frame at %u spp", i,
                         xys[3 * i], xys[3 * i + 1], xys[3 * i + 2], ctx->W, ctx->H, ctx->spp);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t per_ray = 3 * sizeof(uint32_t) + sizeof(uint32_t) + (hit ? 2 * sizeof(float4) : 0) +
-                           (dirs4 ? sizeof(float4) : 0);
-    const size_t chunk = std::min<size_t>(n, cast_chunk(per_ray));
+    const hipStream_t s = ctx->stream;
     Staging st;
-    const size_t b_vec = chunk * sizeof(float4), b_idx = round16(chunk * sizeof(uint32_t)),
-                 b_xys = round16(chunk * 3 * sizeof(uint32_t));
-    const size_t bytes = b_xys + b_idx + (hit ? 2 * b_vec : 0) + (dirs4 ? b_vec : 0);
-    if (hipMalloc((void **)&st.base, bytes) != hipSuccess) {
-        st.base = nullptr;
-        return fail(ctx, SPT_ERR_NOMEM, "spt_primary_hits: %zu bytes of staging", bytes);
-    }
-    uint32_t *d_xys = (uint32_t *)st.base, *d_idx = (uint32_t *)(st.base + b_xys);
-    float4 *d_hit = hit ? (float4 *)(st.base + b_xys + b_idx) : nullptr;
-    float4 *d_dirs = dirs4 ? (float4 *)(st.base + b_xys + b_idx + (hit ? 2 * b_vec : 0)) : nullptr;
+    if (!st.alloc(primary_hits_plan(n, hit != nullptr, dirs4 != nullptr), s))
+        return fail(ctx, SPT_ERR_NOMEM, "spt_primary_hits: %zu bytes of staging", st.plan.total);
+    uint32_t *d_xys = st.at<uint32_t>(0), *d_idx = st.at<uint32_t>(1);
+    float4 *d_hit = st.at<float4>(2), *d_dirs = st.at<float4>(3);
     spt::CastArgs a = cast_args(ctx);
     a.xys = d_xys;
     a.cam = ctx->cam;
@@ -125,7 +110,7 @@ int spt_primary_hits(spt_ctx *ctx, const uint32_t *xys, uint32_t n, uint32_t *id
     a.idx = d_idx;
     a.hit = d_hit;
     a.dirs = d_dirs;
-    const hipStream_t s = ctx->stream;
+    const size_t chunk = st.plan.chunk;
     for (size_t r0 = 0; r0 < n; r0 += chunk) {
         const size_t m = std::min(chunk, (size_t)n - r0);
         HIP_TRY(ctx, hipMemcpyAsync(d_xys, xys + 3 * r0, m * 3 * sizeof(uint32_t), hipMemcpyHostToDevice, s));
@@ -136,7 +121,7 @@ int spt_primary_hits(spt_ctx *ctx, const uint32_t *xys, uint32_t n, uint32_t *id
         if (dirs4) HIP_TRY(ctx, hipMemcpyAsync(dirs4 + 4 * r0, d_dirs, m * sizeof(float4), hipMemcpyDeviceToHost, s));
         HIP_TRY(ctx, hipStreamSynchronize(s));
     }
-    return SPT_OK;
+    return st.done(SPT_OK);
 }
 
 }  // extern "C"

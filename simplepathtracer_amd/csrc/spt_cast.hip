@@ -5,7 +5,7 @@
 // render kernels' own per-wave casts (spt_path.h): find_closest over a flat cluster list
 // or the wave's octant walk of the tree, lane_cast over the block's LDS copy of node
 // layout 0, or find_closest_lane over layout 0 in global memory -- chosen per launch by
-// launch_render's rule (cast_walk below).  Nothing of the traversal is restated here, so
+// the one walk rule (cast_walk, spt_internal.h).  Nothing of the traversal is restated here, so
 // every culling proof of DESIGN.md §4.4 is exercised ray by ray on whatever rays the
 // caller builds.  Primary-ray candidate lists are not used: they hold for camera rays only.
 //
@@ -19,27 +19,23 @@
 //
 // Camera mode (CastArgs::xys): the ray is the primary ray of sample s of pixel (x, y),
 // formed by the render's start_path itself, from the eye.
-#include "spt_path.h"
-
-#include <algorithm>
-#include <mutex>
+#include "spt_query.h"
 
 namespace spt {
 
 namespace {
-
-enum : int { kWalkWave = 0, kWalkLds = 1, kWalkGlane = 2 };
 
 template <bool TREE, int LEAF, int WALK, uint32_t BLOCK>
 __device__ __forceinline__ void cast_body(const CastArgs &a)
 {
     // wave-private scratch of the wave walk's dealt leaf tests (test_leaf_pairs)
     __shared__ uint32_t s_lds[(TREE && WALK == kWalkWave) ? BLOCK : 1];
-    __shared__ uint4 s_nodes[WALK == kWalkLds ? 2 * kLdsNodeRecords : 1];
     const AccelView &ac = a.accel;
+    // lds_node_table's copy (spt_query.h), written out: with the loop inlined from there this
+    // kernel alone gets another scalar register allocation (7 more s_mov in the lane walk's
+    // member loop; sorted rays 1 % slower on the MI355X)
+    __shared__ uint4 s_nodes[WALK == kWalkLds ? 2 * kLdsNodeRecords : 1];
     if (WALK == kWalkLds) {
-        // the host launches this variant only when n_nodes + 1 <= kLdsNodeRecords; skip
-        // links as byte offsets, as render_kernel_lds keeps them (lane_cast BYTES)
         const uint4 *src = (const uint4 *)ac.nodes;
         const uint32_t n4 = 2u * (ac.n_nodes + 1u);
         for (uint32_t k = threadIdx.x; k < n4; k += BLOCK) {
@@ -49,6 +45,7 @@ __device__ __forceinline__ void cast_body(const CastArgs &a)
         }
         __syncthreads();
     }
+    const uint32_t *const nodes = (const uint32_t *)s_nodes;
     const uint32_t lane = __lane_id();
     const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (BLOCK / 64u) + (threadIdx.x >> 6));
     const uint32_t n_waves = gridDim.x * (BLOCK / 64u);
@@ -87,16 +84,7 @@ __device__ __forceinline__ void cast_body(const CastArgs &a)
             d = mk(d4.x, d4.y, d4.z);
         }
         CastDiag dg;
-        Hit h;
-        if (WALK == kWalkLds) {
-            uint32_t ni, leaf, leaf2;
-            (void)lane_cast<LEAF, true>(ac, o, d, active, dg, (const uint32_t *)s_nodes, true, 0xFFFFFFFFu, h, ni, leaf,
-                                        leaf2);
-        } else if (WALK == kWalkGlane) {
-            h = find_closest_lane<LEAF>(ac, o, d, active, dg, (const uint32_t *)ac.nodes);
-        } else {
-            h = find_closest<TREE, LEAF>(ac, o, d, active, dg, nullptr, TREE ? s_lds + (threadIdx.x & ~63u) : nullptr);
-        }
+        const Hit h = query_cast<TREE, LEAF, WALK>(ac, o, d, active, dg, nodes, s_lds + (threadIdx.x & ~63u));
         if (active) {
             const bool miss = h.idx == kMiss;
             a.idx[i] = miss ? a.n_spheres : ac.orig[h.idx];
@@ -139,62 +127,14 @@ __global__ __launch_bounds__(kCastLdsBlock) __attribute__((amdgpu_waves_per_eu(2
     cast_body<true, (int)kClusterSlots, kWalkLds, kCastLdsBlock>(a);
 }
 
-namespace {
-
-// resident blocks of kernel `f` on the current device (cached per device and kernel)
-template <class F>
-uint32_t resident_blocks(F f, uint32_t block, int slot)
-{
-    constexpr int kMaxDevices = 64, kKernels = 5;
-    static std::mutex mu;
-    static uint32_t cache[kMaxDevices][kKernels];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return 0u;
-    std::lock_guard<std::mutex> lk(mu);
-    if (cache[dev][slot] == 0u) {
-        int per_cu = 0, num_cu = 0;
-        if (hipDeviceGetAttribute(&num_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f, (int)block, 0) != hipSuccess || per_cu <= 0 ||
-            num_cu <= 0)
-            return 0u;
-        cache[dev][slot] = (uint32_t)per_cu * (uint32_t)num_cu;
-    }
-    return cache[dev][slot];
-}
-
-template <class F>
-hipError_t launch_one(F f, uint32_t block, int slot, const CastArgs &a, hipStream_t s)
-{
-    const uint32_t resident = resident_blocks(f, block, slot);
-    if (resident == 0u) return hipErrorLaunchFailure;
-    // a wave per run of 64 rays until the device is full, then waves take several runs
-    const uint32_t runs = (a.n + 63u) / 64u, per_block = block / 64u;
-    const uint32_t grid = std::min((runs + per_block - 1u) / per_block, resident);
-    hipLaunchKernelGGL(f, dim3(grid), dim3(block), 0, s, a);
-    return hipGetLastError();
-}
-
-}  // namespace
-
-// launch_render's rule (spt_kernels.hip) for the context's current traversal shape
-uint32_t cast_walk(const AccelView &ac)
-{
-    if (ac.tree && ac.n_nodes >= kLdsMinNodes && ac.n_nodes + 1u <= kLdsNodeRecords) return kCastWalkLds;
-    if (ac.tree && ac.n_nodes >= kLdsMinNodes && ac.n_nodes <= kGlaneMaxNodes) return kCastWalkGlane;
-    if (ac.tree) return kCastWalkWave;
-    return ac.leaf_slots == kFlatLeafSlots ? kCastWalkFlat4 : kCastWalkFlat8;
-}
-
 hipError_t launch_cast(const CastArgs &a, hipStream_t s)
 {
     if (a.n == 0u) return hipSuccess;
-    switch (cast_walk(a.accel)) {
-    case kCastWalkLds: return launch_one(cast_kernel_lds, kCastLdsBlock, 0, a, s);
-    case kCastWalkGlane: return launch_one(cast_kernel_glane, kCastBlock, 1, a, s);
-    case kCastWalkWave: return launch_one(cast_kernel<true, (int)kClusterSlots>, kCastBlock, 2, a, s);
-    case kCastWalkFlat4: return launch_one(cast_kernel<false, (int)kFlatLeafSlots>, kCastBlock, 3, a, s);
-    default: return launch_one(cast_kernel<false, (int)kClusterSlots>, kCastBlock, 4, a, s);
-    }
+    // (in the order of cast_walk's values)
+    void (*const kernels[5])(CastArgs) = {cast_kernel_lds, cast_kernel_glane, cast_kernel<true, (int)kClusterSlots>,
+                                          cast_kernel<false, (int)kFlatLeafSlots>, cast_kernel<false, (int)kClusterSlots>};
+    // a wave per run of 64 rays
+    return launch_query(a.accel, kernels, kCastBlock, kCastLdsBlock, (a.n + 63u) / 64u, s, a);
 }
 
 }  // namespace spt

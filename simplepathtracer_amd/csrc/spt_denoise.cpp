@@ -135,29 +135,20 @@ int spt_denoise(spt_ctx *ctx, uint32_t width, uint32_t height, const float *rgba
     if (nothing) return SPT_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     // one allocation: rgba, feat, out, the scratch planes, then the bytes
-    const size_t npix = (size_t)width * height;
-    const size_t b_rgba = npix * sizeof(float4), b_feat = 2 * b_rgba, b_out = out_rgba ? b_rgba : 0;
-    const size_t b_scr = (size_t)scratch_bytes(npix, levels), b_rgb8 = out_rgb8 ? npix * 3 : 0;
-    Staging st;
-    if (hipMalloc((void **)&st.base, b_rgba + b_feat + b_out + b_scr + b_rgb8) != hipSuccess) {
-        st.base = nullptr;
-        return fail(ctx, SPT_ERR_NOMEM, "spt_denoise: %zu bytes of device buffers", b_rgba + b_feat + b_out + b_scr + b_rgb8);
-    }
-    float4 *d_rgba = (float4 *)st.base, *d_feat = d_rgba + npix;
-    float4 *d_out = out_rgba ? d_feat + 2 * npix : nullptr;
-    float4 *d_scr = b_scr ? (float4 *)(st.base + b_rgba + b_feat + b_out) : nullptr;
-    uint8_t *d_rgb8 = out_rgb8 ? (uint8_t *)(st.base + b_rgba + b_feat + b_out + b_scr) : nullptr;
+    const size_t npix = (size_t)width * height, b_rgba = npix * sizeof(float4);
     const hipStream_t s = ctx->stream;
+    Staging st;
+    if (!st.alloc(denoise_plan(npix, (size_t)scratch_planes(levels), out_rgba != nullptr, out_rgb8 != nullptr), s))
+        return fail(ctx, SPT_ERR_NOMEM, "spt_denoise: %zu bytes of device buffers", st.plan.total);
+    float4 *d_rgba = st.at<float4>(0), *d_feat = st.at<float4>(1), *d_out = st.at<float4>(2), *d_scr = st.at<float4>(3);
+    uint8_t *d_rgb8 = st.at<uint8_t>(4);
     HIP_TRY(ctx, hipMemcpyAsync(d_rgba, rgba, b_rgba, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemcpyAsync(d_feat, feat, b_feat, hipMemcpyHostToDevice, s));
-    if (int rc = denoise_launch(ctx, width, height, d_rgba, d_feat, sigma, levels, d_out, d_rgb8, d_scr, s)) {
-        (void)hipStreamSynchronize(s);  // the buffers are freed on return
-        return rc;
-    }
-    if (out_rgba) HIP_TRY(ctx, hipMemcpyAsync(out_rgba, d_out, b_out, hipMemcpyDeviceToHost, s));
-    if (out_rgb8) HIP_TRY(ctx, hipMemcpyAsync(out_rgb8, d_rgb8, b_rgb8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d_feat, feat, 2 * b_rgba, hipMemcpyHostToDevice, s));
+    if (int rc = denoise_launch(ctx, width, height, d_rgba, d_feat, sigma, levels, d_out, d_rgb8, d_scr, s)) return rc;
+    if (out_rgba) HIP_TRY(ctx, hipMemcpyAsync(out_rgba, d_out, b_rgba, hipMemcpyDeviceToHost, s));
+    if (out_rgb8) HIP_TRY(ctx, hipMemcpyAsync(out_rgb8, d_rgb8, npix * 3, hipMemcpyDeviceToHost, s));
     HIP_TRY(ctx, hipStreamSynchronize(s));
-    return SPT_OK;
+    return st.done(SPT_OK);
 }
 
 }  // extern "C"

@@ -123,17 +123,13 @@ int spt_render_features(spt_ctx *ctx, uint32_t yB, uint32_t yE, uint32_t xB, uin
     // per pixel: two float4 and one word out; chunks of whole 8-row bands, so a chunk's
     // tiles are the region's own
     const size_t w = xE - xB, h = yE - yB;
-    const size_t per_row = w * ((feat ? 2 * sizeof(float4) : 0) + (ids ? sizeof(uint32_t) : 0));
-    const size_t chunk = std::min(h, std::max<size_t>(8, (kCastStagingBytes / per_row) & ~(size_t)7));
-    Staging st;
-    const size_t b_feat = feat ? chunk * w * 2 * sizeof(float4) : 0, b_ids = ids ? round16(chunk * w * sizeof(uint32_t)) : 0;
-    if (hipMalloc((void **)&st.base, b_feat + b_ids) != hipSuccess) {
-        st.base = nullptr;
-        return fail(ctx, SPT_ERR_NOMEM, "spt_render_features: %zu bytes of staging", b_feat + b_ids);
-    }
-    float4 *d_feat = feat ? (float4 *)st.base : nullptr;
-    uint32_t *d_ids = ids ? (uint32_t *)(st.base + b_feat) : nullptr;
     const hipStream_t s = ctx->stream;
+    Staging st;
+    if (!st.alloc(features_plan(w, h, feat != nullptr, ids != nullptr), s))
+        return fail(ctx, SPT_ERR_NOMEM, "spt_render_features: %zu bytes of staging", st.plan.total);
+    float4 *d_feat = st.at<float4>(0);
+    uint32_t *d_ids = st.at<uint32_t>(1);
+    const size_t chunk = st.plan.chunk;
     for (size_t r0 = 0; r0 < h; r0 += chunk) {
         const size_t m = std::min(chunk, h - r0);
         const spt::RowMap map{yB + (uint32_t)r0, yB + (uint32_t)(r0 + m), 1u, 1u, 0u, xB, (uint32_t)w};
@@ -142,7 +138,7 @@ int spt_render_features(spt_ctx *ctx, uint32_t yB, uint32_t yE, uint32_t xB, uin
         if (ids) HIP_TRY(ctx, hipMemcpyAsync(ids + r0 * w, d_ids, m * w * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(ctx, hipStreamSynchronize(s));
     }
-    return SPT_OK;
+    return st.done(SPT_OK);
 }
 
 }  // extern "C"

@@ -23,36 +23,19 @@
 //
 // prim_list_cast reads the kernel's first argument as a RenderArgs (kernarg_args), so the
 // kernels take a RenderArgs first and FeatArgs second.
-#include "spt_path.h"
-
-#include <algorithm>
-#include <mutex>
+#include "spt_query.h"
 
 namespace spt {
 
 namespace {
-
-enum : int { kWalkWave = 0, kWalkLds = 1, kWalkGlane = 2 };
 
 template <bool TREE, int LEAF, int WALK, uint32_t BLOCK>
 __device__ __forceinline__ void features_body(const RenderArgs &k, const FeatArgs &f)
 {
     // wave-private scratch of the wave walk's dealt leaf tests (test_leaf_pairs)
     __shared__ uint32_t s_lds[(TREE && WALK == kWalkWave) ? BLOCK : 1];
-    __shared__ uint4 s_nodes[WALK == kWalkLds ? 2 * kLdsNodeRecords : 1];
     const AccelView &ac = k.scene.accel;
-    if (WALK == kWalkLds) {
-        // the host launches this variant only when n_nodes + 1 <= kLdsNodeRecords; skip
-        // links as byte offsets, as render_kernel_lds keeps them (lane_cast BYTES)
-        const uint4 *src = (const uint4 *)ac.nodes;
-        const uint32_t n4 = 2u * (ac.n_nodes + 1u);
-        for (uint32_t q = threadIdx.x; q < n4; q += BLOCK) {
-            uint4 v = src[q];
-            if (q & 1u) v.x <<= 5;
-            s_nodes[q] = v;
-        }
-        __syncthreads();
-    }
+    const uint32_t *const nodes = lds_node_table<WALK, BLOCK>(ac);
     const uint32_t lane = __lane_id();
     const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (BLOCK / 64u) + (threadIdx.x >> 6));
     const uint32_t n_waves = gridDim.x * (BLOCK / 64u);
@@ -77,18 +60,7 @@ __device__ __forceinline__ void features_body(const RenderArgs &k, const FeatArg
             Hit h1;
             bool listed = false;
             if (kernarg_args()->prim.on) listed = prim_list_cast(ac, ps.o, ps.d, active, pxy, h1, dg);
-            if (!listed) {
-                if (WALK == kWalkLds) {
-                    uint32_t ni, leaf, leaf2;
-                    (void)lane_cast<LEAF, true>(ac, ps.o, ps.d, active, dg, (const uint32_t *)s_nodes, true, 0xFFFFFFFFu,
-                                                h1, ni, leaf, leaf2);
-                } else if (WALK == kWalkGlane) {
-                    h1 = find_closest_lane<LEAF>(ac, ps.o, ps.d, active, dg, (const uint32_t *)ac.nodes);
-                } else {
-                    h1 = find_closest<TREE, LEAF>(ac, ps.o, ps.d, active, dg, nullptr,
-                                                  TREE ? s_lds + (threadIdx.x & ~63u) : nullptr);
-                }
-            }
+            if (!listed) h1 = query_cast<TREE, LEAF, WALK>(ac, ps.o, ps.d, active, dg, nodes, s_lds + (threadIdx.x & ~63u));
             if (active) {
                 const bool miss = h1.idx == kMiss;
                 // the sky term of SampleColorSkybox, as decode_sample rebuilds it
@@ -163,53 +135,16 @@ __global__ __launch_bounds__(kFeatLdsBlock) __attribute__((amdgpu_waves_per_eu(2
     features_body<true, (int)kClusterSlots, kWalkLds, kFeatLdsBlock>(k, f);
 }
 
-namespace {
-
-// resident blocks of kernel `f` on the current device (cached per device and kernel)
-template <class F>
-uint32_t resident_blocks(F f, uint32_t block, int slot)
-{
-    constexpr int kMaxDevices = 64, kKernels = 5;
-    static std::mutex mu;
-    static uint32_t cache[kMaxDevices][kKernels];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return 0u;
-    std::lock_guard<std::mutex> lk(mu);
-    if (cache[dev][slot] == 0u) {
-        int per_cu = 0, num_cu = 0;
-        if (hipDeviceGetAttribute(&num_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f, (int)block, 0) != hipSuccess || per_cu <= 0 ||
-            num_cu <= 0)
-            return 0u;
-        cache[dev][slot] = (uint32_t)per_cu * (uint32_t)num_cu;
-    }
-    return cache[dev][slot];
-}
-
-template <class F>
-hipError_t launch_one(F fn, uint32_t block, int slot, const RenderArgs &k, const FeatArgs &f, hipStream_t s)
-{
-    const uint32_t resident = resident_blocks(fn, block, slot);
-    if (resident == 0u) return hipErrorLaunchFailure;
-    // a wave per tile until the device is full, then waves take several tiles
-    const uint32_t per_block = block / 64u;
-    const uint32_t grid = std::min((f.tiles + per_block - 1u) / per_block, resident);
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(block), 0, s, k, f);
-    return hipGetLastError();
-}
-
-}  // namespace
-
 hipError_t launch_features(const RenderArgs &k, const FeatArgs &f, hipStream_t s)
 {
     if (f.tiles == 0u) return hipSuccess;
-    switch (cast_walk(k.scene.accel)) {
-    case kCastWalkLds: return launch_one(features_kernel_lds, kFeatLdsBlock, 0, k, f, s);
-    case kCastWalkGlane: return launch_one(features_kernel_glane, kFeatBlock, 1, k, f, s);
-    case kCastWalkWave: return launch_one(features_kernel<true, (int)kClusterSlots>, kFeatBlock, 2, k, f, s);
-    case kCastWalkFlat4: return launch_one(features_kernel<false, (int)kFlatLeafSlots>, kFeatBlock, 3, k, f, s);
-    default: return launch_one(features_kernel<false, (int)kClusterSlots>, kFeatBlock, 4, k, f, s);
-    }
+    // (in the order of cast_walk's values)
+    void (*const kernels[5])(RenderArgs, FeatArgs) = {features_kernel_lds, features_kernel_glane,
+                                                      features_kernel<true, (int)kClusterSlots>,
+                                                      features_kernel<false, (int)kFlatLeafSlots>,
+                                                      features_kernel<false, (int)kClusterSlots>};
+    // a wave per tile
+    return launch_query(k.scene.accel, kernels, kFeatBlock, kFeatLdsBlock, f.tiles, s, k, f);
 }
 
 }  // namespace spt

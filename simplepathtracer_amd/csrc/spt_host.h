@@ -7,6 +7,12 @@
 //                    HIP-free half (tile recognition, bookkeeping, reader gate)
 //   spt_service.cpp  the render service's host half (sessions, publication, flow control)
 //   spt_multi.cpp    multi-device frames (spt_render_frame) and page-locked g_data
+//   spt_cast.cpp     ray queries (spt_cast_rays[_async], spt_primary_hits)
+//   spt_trace.cpp    path queries (spt_trace_rays[_async], spt_sample_state)
+//   spt_features.cpp feature buffers (spt_render_features[_async])
+//   spt_denoise.cpp  the denoiser (spt_denoise[_async])
+//   spt_staging.cpp  the device staging of their blocking forms; spt_staging.h is its
+//                    HIP-free half (the plan: chunk size, offsets, total)
 // The context owns the device copy of the reference's global state (scene SoA, camera,
 // config: Globals.hpp:8-37), the per-sample workspaces and the launch geometry of the
 // persistent render kernel, and rebuilds the two reference entry points RenderSegment
@@ -17,6 +23,7 @@
 #include "spt_accel.h"
 #include "spt_internal.h"
 #include "spt_readahead.h"
+#include "spt_staging.h"
 
 #include <hip/hip_runtime.h>
 
@@ -490,22 +497,6 @@ int grow_host_rects(spt_ctx *ctx, BatchSet *bs, size_t n);
 void destroy_batch_set(BatchSet *b);
 int reset_one(spt_ctx *ctx);
 int stats_one(spt_ctx *ctx, spt_stats *out);
-
-// Staging of the blocking ray and path queries (spt_cast.cpp, spt_trace.cpp): at most 256 MiB
-// on the device, as spt_render_samples
-constexpr size_t kCastStagingBytes = (size_t)256 << 20;
-// One device allocation cut into the chunk's arrays (each a multiple of 16 bytes per ray
-// or rounded up to one).
-struct Staging {
-    char *base = nullptr;
-    ~Staging()
-    {
-        if (base) (void)hipFree(base);
-    }
-};
-inline size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
-// rays per chunk at per_ray staging bytes each: whole waves, within the staging bound
-inline size_t cast_chunk(size_t per_ray) { return std::max<size_t>(64, ((kCastStagingBytes - 64) / per_ray) & ~(size_t)63); }
 
 template <class T>
 int ensure(spt_ctx *ctx, T **p, size_t *cap, size_t count)

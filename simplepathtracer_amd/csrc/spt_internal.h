@@ -459,11 +459,7 @@ constexpr uint32_t kSvcTraceClaims = 1u << 21;  // SPT_SVC_TRACE: claims with a 
 // grid: blocks of the session kernel's shape (svc_grid: 256-thread blocks, or the LDS-tree
 // kernel's 1 024-thread blocks when the scene's tree takes the LDS lane walk)
 hipError_t launch_render_svc(const RenderArgs &a, uint32_t grid, hipStream_t s);
-// the service covers the wave-walk kernels (render_kernel's shapes) and the LDS lane walk
-// (render_kernel_lds's shape, round 6); trees walked from global memory keep their launches
-bool svc_supported(const AccelView &ac);
-// does the scene's session run the LDS-tree kernel (1 024-thread blocks)?
-bool svc_lds(const AccelView &ac);
+// (svc_supported, svc_lds: which scenes the service takes, below with the walk rule)
 // the LDS-tree session's grid: every block slot (full) or one per CU fewer, at least one
 // per CU; 0 when the LDS-tree kernel cannot run on this device
 uint32_t svc_lds_grid(bool full);
@@ -545,11 +541,8 @@ constexpr uint32_t kTaskPasses = 10;     // TaskBasedPathTracer.hpp:81
 #endif
 constexpr uint32_t kRenderBlock = SPT_RENDER_BLOCK;
 uint32_t render_block_size();  // kRenderBlock of the kernel object (the launch uses it)
-// true when launch_render walks this tree lane by lane (LDS or global-memory lane walk)
-bool lane_walk_tree(const AccelView &ac);
 
-// Node counts that choose a tree's walk (launch_render, spt_kernels.hip; launch_cast,
-// spt_cast.hip).
+// Node counts that choose a tree's walk (cast_walk below).
 // 32-byte node records (pad included) of the LDS copy per block: 2432 = 76 KiB, with the
 // sampler's 4 KiB exactly half of the CU's 160 KiB
 #ifndef SPT_LDS_NODES
@@ -570,6 +563,35 @@ constexpr uint32_t kLdsMinNodes = SPT_LDS_MIN_NODES;
 #define SPT_GLANE_MAX_NODES 9000
 #endif
 constexpr uint32_t kGlaneMaxNodes = SPT_GLANE_MAX_NODES;
+// (cast_walk below relies on it; a build with -DSPT_GLANE_MAX_NODES below the LDS bound,
+// which no variant of the Makefile makes, stops here instead of walking such trees from LDS)
+static_assert(kLdsNodeRecords <= kGlaneMaxNodes + 1u, "the global lane walk takes over where the LDS copy ends");
+// the LDS-tree session kernel (render_kernel_svc_lds) also holds its waves' job records
+// (16 x kSvcRecWords words = 80 records' worth): its table is that much shorter, so that
+// two blocks still fit a CU (at 81 920 B the compiler keeps 64 VGPRs, 8 waves per SIMD)
+constexpr uint32_t kLdsSvcNodeRecords = kLdsNodeRecords - 80u;
+
+// The walk of a traversal shape, the one rule every launcher follows (launch_render,
+// launch_render_svc, the wavefront engine, the query kernels): flat cluster lists of 4 or 8
+// leaf slots; trees of kLdsMinNodes nodes or more lane by lane, over the block's LDS copy
+// of node layout 0 while it fits, then over global memory up to kGlaneMaxNodes; every
+// other tree by the wave's octant walk.
+enum : uint32_t { kCastWalkLds = 0, kCastWalkGlane = 1, kCastWalkWave = 2, kCastWalkFlat4 = 3, kCastWalkFlat8 = 4 };
+inline uint32_t cast_walk(const AccelView &ac)
+{
+    if (!ac.tree) return ac.leaf_slots == kFlatLeafSlots ? kCastWalkFlat4 : kCastWalkFlat8;
+    if (ac.n_nodes < kLdsMinNodes || ac.n_nodes > kGlaneMaxNodes) return kCastWalkWave;
+    return ac.n_nodes + 1u <= kLdsNodeRecords ? kCastWalkLds : kCastWalkGlane;
+}
+// true when the tree is walked lane by lane (LDS or global-memory lane walk)
+inline bool lane_walk_tree(const AccelView &ac) { return cast_walk(ac) == kCastWalkLds || cast_walk(ac) == kCastWalkGlane; }
+// does the scene's service session run the LDS-tree kernel (1 024-thread blocks)?  Its own,
+// shorter table bound
+inline bool svc_lds(const AccelView &ac) { return cast_walk(ac) == kCastWalkLds && ac.n_nodes + 1u <= kLdsSvcNodeRecords; }
+// the service covers the wave-walk kernels (render_kernel's shapes) and the LDS lane walk
+// (render_kernel_lds's shape, round 6); trees walked from global memory, or from an LDS
+// table longer than the session's, keep their launches
+inline bool svc_supported(const AccelView &ac) { return !lane_walk_tree(ac) || svc_lds(ac); }
 
 // ---- ray queries (spt_cast.hip; spt_cast_rays[_async], spt_primary_hits) ---------------
 // n rays, one per lane, cast with the render kernels' traversals.  Ray mode: origins o and
@@ -588,9 +610,6 @@ struct CastArgs {
     uint32_t *idx;
     float4 *hit, *dirs;
 };
-// the kernel launch_cast picks for a traversal shape: launch_render's rule
-enum : uint32_t { kCastWalkFlat4 = 0, kCastWalkFlat8 = 1, kCastWalkWave = 2, kCastWalkLds = 3, kCastWalkGlane = 4 };
-uint32_t cast_walk(const AccelView &ac);
 hipError_t launch_cast(const CastArgs &a, hipStream_t s);
 
 // ---- path queries (spt_trace.hip; spt_trace_rays[_async]) ------------------------------

@@ -59,12 +59,8 @@ namespace spt {
 #define SPT_LDS_BLOCK 1024
 #endif
 constexpr uint32_t kLdsBlock = SPT_LDS_BLOCK;
-// (kLdsNodeRecords, kLdsMinNodes and kGlaneMaxNodes, the node counts that choose the walk,
-// are in spt_internal.h: the cast kernels of spt_cast.hip follow the same rule)
-// the LDS-tree session kernel (render_kernel_svc_lds) also holds its waves' job records
-// (16 x kSvcRecWords words = 80 records' worth): its table is that much shorter, so that
-// two blocks still fit a CU (at 81 920 B the compiler keeps 64 VGPRs, 8 waves per SIMD)
-constexpr uint32_t kLdsSvcNodeRecords = kLdsNodeRecords - 80u;
+// (the node counts that choose the walk, and the rule itself (cast_walk), are in
+// spt_internal.h with kLdsSvcNodeRecords, the LDS-tree session kernel's shorter table)
 #ifndef SPT_LANE_BUDGET
 #define SPT_LANE_BUDGET 7
 #endif
@@ -1266,7 +1262,7 @@ hipError_t launch_render(const RenderArgs &a, LaunchShape &sh, hipStream_t s)
     // trees of >= kLdsMinNodes nodes walk an LDS copy of the node table (config 5);
     // smaller ones stay in the scalar cache (all 8 octant layouts: config 2's 26-node
     // tree is 6.7 KB), where the 256-thread kernel overlaps frames in flight better
-    if (a.scene.accel.tree && a.scene.accel.n_nodes >= kLdsMinNodes && a.scene.accel.n_nodes + 1u <= kLdsNodeRecords) {
+    if (cast_walk(a.scene.accel) == kCastWalkLds) {
         // all resident blocks (divided among the host calls in flight), or fewer when the
         // launch has under 2 claims per wave (render_grid's rule)
         int per_cu = 0, num_cu = 0;
@@ -1288,7 +1284,8 @@ hipError_t launch_render(const RenderArgs &a, LaunchShape &sh, hipStream_t s)
     }
     sh.ran_grid = sh.grid;
     sh.ran_block = sh.block;
-    if (a.scene.accel.tree && a.scene.accel.n_nodes >= kLdsMinNodes && a.scene.accel.n_nodes <= kGlaneMaxNodes) {
+    // (also the LDS walk's trees, where the LDS kernel cannot run on this device)
+    if (lane_walk_tree(a.scene.accel)) {
         if (batch)
             hipLaunchKernelGGL(render_kernel_glane_batch, dim3(sh.grid), dim3(sh.block), 0, s, a);
         else
@@ -1309,16 +1306,6 @@ hipError_t launch_render(const RenderArgs &a, LaunchShape &sh, hipStream_t s)
     else
         hipLaunchKernelGGL((render_kernel<false, (int)kClusterSlots>), dim3(sh.grid), dim3(sh.block), 0, s, a);
     return hipGetLastError();
-}
-
-bool svc_lds(const AccelView &ac)
-{
-    return ac.tree && ac.n_nodes >= kLdsMinNodes && ac.n_nodes + 1u <= kLdsSvcNodeRecords;
-}
-
-bool svc_supported(const AccelView &ac)
-{
-    return !(ac.tree && ac.n_nodes >= kLdsMinNodes && ac.n_nodes <= kGlaneMaxNodes) || svc_lds(ac);
 }
 
 uint32_t svc_block(const AccelView &ac) { return svc_lds(ac) ? kLdsBlock : kRenderBlock; }
@@ -1377,10 +1364,6 @@ hipError_t launch_selftest(const float *a, const float *b, const uint32_t *bits,
 
 uint32_t render_group_size() { return SPT_GROUP; }
 uint32_t render_block_size() { return kRenderBlock; }
-bool lane_walk_tree(const AccelView &ac)
-{
-    return ac.tree && ac.n_nodes >= kLdsMinNodes && (ac.n_nodes + 1u <= kLdsNodeRecords || ac.n_nodes <= kGlaneMaxNodes);
-}
 
 hipError_t render_occupancy(uint32_t block, int *blocks_per_cu)
 {

@@ -81,26 +81,20 @@ int spt_trace_rays(spt_ctx *ctx, const float *origins4, const float *dirs4, cons
     if (int rc = trace_check(ctx, n, bounces, origins4 && dirs4 && states && rgba, &nothing)) return rc;
     if (nothing) return SPT_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // per ray: origin + direction + state in, colour (+ two words) out
-    const size_t per_ray = 3 * sizeof(float4) + sizeof(uint64_t) + (info ? 2 * sizeof(uint32_t) : 0);
-    const size_t chunk = std::min<size_t>(n, cast_chunk(per_ray));
+    const hipStream_t s = ctx->stream;
     Staging st;
-    const size_t b_vec = chunk * sizeof(float4), b_two = round16(chunk * 2 * sizeof(uint32_t));
-    const size_t bytes = 3 * b_vec + b_two + (info ? b_two : 0);
-    if (hipMalloc((void **)&st.base, bytes) != hipSuccess) {
-        st.base = nullptr;
-        return fail(ctx, SPT_ERR_NOMEM, "spt_trace_rays: %zu bytes of staging", bytes);
-    }
-    float4 *d_o = (float4 *)st.base, *d_d = (float4 *)(st.base + b_vec), *d_rgba = (float4 *)(st.base + 2 * b_vec);
-    uint64_t *d_st = (uint64_t *)(st.base + 3 * b_vec);
-    uint32_t *d_info = info ? (uint32_t *)(st.base + 3 * b_vec + b_two) : nullptr;
+    if (!st.alloc(trace_rays_plan(n, info != nullptr), s))
+        return fail(ctx, SPT_ERR_NOMEM, "spt_trace_rays: %zu bytes of staging", st.plan.total);
+    float4 *d_o = st.at<float4>(0), *d_d = st.at<float4>(1), *d_rgba = st.at<float4>(2);
+    uint64_t *d_st = st.at<uint64_t>(3);
+    uint32_t *d_info = st.at<uint32_t>(4);
     spt::TraceArgs a = trace_args(ctx, bounces);
     a.o = d_o;
     a.d = d_d;
     a.st = d_st;
     a.rgba = d_rgba;
     a.info = d_info;
-    const hipStream_t s = ctx->stream;
+    const size_t chunk = st.plan.chunk;
     for (size_t r0 = 0; r0 < n; r0 += chunk) {
         const size_t m = std::min(chunk, (size_t)n - r0);
         HIP_TRY(ctx, hipMemcpyAsync(d_o, origins4 + 4 * r0, m * sizeof(float4), hipMemcpyHostToDevice, s));
@@ -112,7 +106,7 @@ int spt_trace_rays(spt_ctx *ctx, const float *origins4, const float *dirs4, cons
         if (info) HIP_TRY(ctx, hipMemcpyAsync(info + 2 * r0, d_info, m * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(ctx, hipStreamSynchronize(s));
     }
-    return SPT_OK;
+    return st.done(SPT_OK);
 }
 
 int spt_sample_state(uint64_t seed, uint32_t pixel, uint32_t sample, uint32_t draws, uint64_t *state)

@@ -23,17 +23,12 @@
 // kernel on the same stream turns each word into its colour in place with the fold's own
 // decode_sample (spt_decode.h).  (Decoding in the trace kernel would need the word back
 // from memory: a store-to-load round trip in every iteration in which a path ends.)
-#include "spt_path.h"
+#include "spt_query.h"
 #include "spt_decode.h"
-
-#include <algorithm>
-#include <mutex>
 
 namespace spt {
 
 namespace {
-
-enum : int { kWalkWave = 0, kWalkLds = 1, kWalkGlane = 2 };
 
 // rays per launch: item = 4 i stays below 2^32 (launch_trace cuts larger batches)
 constexpr uint32_t kTraceLaunchRays = 1u << 28;
@@ -48,20 +43,8 @@ __device__ __forceinline__ void trace_body(const TraceArgs &a)
     constexpr bool AHEAD = WALK != kWalkLds;
     // wave-private scratch of the cooperative sampler and the wave walk's dealt leaf tests
     __shared__ uint32_t s_lds[BLOCK];
-    __shared__ uint4 s_nodes[WALK == kWalkLds ? 2 * kLdsNodeRecords : 1];
     const AccelView &ac = a.scene.accel;
-    if (WALK == kWalkLds) {
-        // the host launches this variant only when n_nodes + 1 <= kLdsNodeRecords; skip
-        // links as byte offsets, as render_kernel_lds keeps them (lane_cast BYTES)
-        const uint4 *src = (const uint4 *)ac.nodes;
-        const uint32_t n4 = 2u * (ac.n_nodes + 1u);
-        for (uint32_t k = threadIdx.x; k < n4; k += BLOCK) {
-            uint4 v = src[k];
-            if (k & 1u) v.x <<= 5;
-            s_nodes[k] = v;
-        }
-        __syncthreads();
-    }
+    const uint32_t *const nodes = lds_node_table<WALK, BLOCK>(ac);
     // what shade_step reads of a render launch: the scene, the depth, segment mode, and
     // the sample slots (the rgba output as words, path i's slot at word 4 i)
     RenderArgs ra;
@@ -154,16 +137,7 @@ __device__ __forceinline__ void trace_body(const TraceArgs &a)
         }
         // ---- one cast + one shading step ----
         const bool act = ps.phase != PH_IDLE;
-        Hit h;
-        if (WALK == kWalkLds) {
-            uint32_t ni, leaf, leaf2;
-            (void)lane_cast<LEAF, true>(ac, ps.o, ps.d, act, dg, (const uint32_t *)s_nodes, true, 0xFFFFFFFFu, h, ni,
-                                        leaf, leaf2);
-        } else if (WALK == kWalkGlane) {
-            h = find_closest_lane<LEAF>(ac, ps.o, ps.d, act, dg, (const uint32_t *)ac.nodes);
-        } else {
-            h = find_closest<TREE, LEAF>(ac, ps.o, ps.d, act, dg, nullptr, TREE ? lds : nullptr);
-        }
+        const Hit h = query_cast<TREE, LEAF, WALK>(ac, ps.o, ps.d, act, dg, nodes, lds);
         casts += act ? 1u : 0u;
         shade_step(ra, ps, h, act, done, dropped, lds);
         if (act && ps.phase == PH_IDLE && a.info) {
@@ -209,45 +183,11 @@ __global__ __launch_bounds__(256) void trace_decode_kernel(FoldArgs f, float4 *r
     rgba[i] = make_float4(c.x, c.y, c.z, 0.f);
 }
 
-namespace {
-
-// resident blocks of kernel `f` on the current device (cached per device and kernel)
-template <class F>
-uint32_t resident_blocks(F f, uint32_t block, int slot)
-{
-    constexpr int kMaxDevices = 64, kKernels = 5;
-    static std::mutex mu;
-    static uint32_t cache[kMaxDevices][kKernels];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return 0u;
-    std::lock_guard<std::mutex> lk(mu);
-    if (cache[dev][slot] == 0u) {
-        int per_cu = 0, num_cu = 0;
-        if (hipDeviceGetAttribute(&num_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f, (int)block, 0) != hipSuccess || per_cu <= 0 ||
-            num_cu <= 0)
-            return 0u;
-        cache[dev][slot] = (uint32_t)per_cu * (uint32_t)num_cu;
-    }
-    return cache[dev][slot];
-}
-
-template <class F>
-hipError_t launch_one(F f, uint32_t block, int slot, const TraceArgs &a, hipStream_t s)
-{
-    const uint32_t resident = resident_blocks(f, block, slot);
-    if (resident == 0u) return hipErrorLaunchFailure;
-    // a wave per run of 64 rays until the device is full, then waves take several runs
-    const uint32_t runs = (a.n + 63u) / 64u, per_block = block / 64u;
-    const uint32_t grid = std::min((runs + per_block - 1u) / per_block, resident);
-    hipLaunchKernelGGL(f, dim3(grid), dim3(block), 0, s, a);
-    return hipGetLastError();
-}
-
-}  // namespace
-
 hipError_t launch_trace(const TraceArgs &all, const FoldArgs &fa, hipStream_t s)
 {
+    // (in the order of cast_walk's values)
+    void (*const kernels[5])(TraceArgs) = {trace_kernel_lds, trace_kernel_glane, trace_kernel<true, (int)kClusterSlots>,
+                                           trace_kernel<false, (int)kFlatLeafSlots>, trace_kernel<false, (int)kClusterSlots>};
     for (uint64_t r0 = 0; r0 < all.n; r0 += kTraceLaunchRays) {
         TraceArgs a = all;
         a.n = (uint32_t)std::min<uint64_t>(kTraceLaunchRays, all.n - r0);
@@ -256,14 +196,8 @@ hipError_t launch_trace(const TraceArgs &all, const FoldArgs &fa, hipStream_t s)
         a.st += r0;
         a.rgba += r0;
         if (a.info) a.info += 2u * r0;
-        hipError_t e;
-        switch (cast_walk(a.scene.accel)) {
-        case kCastWalkLds: e = launch_one(trace_kernel_lds, kTraceLdsBlock, 0, a, s); break;
-        case kCastWalkGlane: e = launch_one(trace_kernel_glane, kTraceBlock, 1, a, s); break;
-        case kCastWalkWave: e = launch_one(trace_kernel<true, (int)kClusterSlots>, kTraceBlock, 2, a, s); break;
-        case kCastWalkFlat4: e = launch_one(trace_kernel<false, (int)kFlatLeafSlots>, kTraceBlock, 3, a, s); break;
-        default: e = launch_one(trace_kernel<false, (int)kClusterSlots>, kTraceBlock, 4, a, s); break;
-        }
+        // a wave per run of 64 rays
+        hipError_t e = launch_query(a.scene.accel, kernels, kTraceBlock, kTraceLdsBlock, (a.n + 63u) / 64u, s, a);
         if (e != hipSuccess) return e;
         FoldArgs f = fa;
         f.samples = (const uint32_t *)a.rgba;

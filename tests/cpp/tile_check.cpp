@@ -4,7 +4,8 @@
 // config sizes, full 8x8 tiles are contiguous runs of 64 items, and
 // spt::ts_slot_base inverts ts_item (the fold's slot of (pixel, sample)).  The
 // sample codes: code_word / word_code round trip, and no sky word k = fl(y + 1.f)
-// (any float y) falls in the code range.  Exit 0 = pass.
+// (any float y) falls in the code range.  The walk rule: spt::cast_walk, lane_walk_tree
+// and svc_supported against a table of literal values.  Exit 0 = pass.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -181,6 +182,41 @@ int main()
                 return 1;
             }
         } while (++bits != 0);
+    }
+    // the walk rule (spt::cast_walk) and its two predicates at the node counts where the
+    // walk changes: trees of 64 .. 2431 nodes walk the LDS copy, 2432 .. 9000 global memory
+    // lane by lane, every other tree the wave walk; flat lists by their leaf slots
+    {
+        const uint32_t F4 = spt::kCastWalkFlat4, F8 = spt::kCastWalkFlat8, WV = spt::kCastWalkWave, LD = spt::kCastWalkLds,
+                       GL = spt::kCastWalkGlane;
+        const struct {
+            uint32_t tree, leaf_slots, n_nodes, walk;
+            bool lane, svc;
+        } rule[] = {
+            {0, 4, 0, F4, false, true},    {0, 4, 63, F4, false, true},   {0, 4, 64, F4, false, true},
+            {0, 4, 2431, F4, false, true}, {0, 4, 2432, F4, false, true}, {0, 4, 9000, F4, false, true},
+            {0, 4, 9001, F4, false, true}, {0, 8, 0, F8, false, true},    {0, 8, 63, F8, false, true},
+            {0, 8, 64, F8, false, true},   {0, 8, 2431, F8, false, true}, {0, 8, 2432, F8, false, true},
+            {0, 8, 9000, F8, false, true}, {0, 8, 9001, F8, false, true}, {1, 4, 0, WV, false, true},
+            {1, 4, 63, WV, false, true},   {1, 4, 64, LD, true, true},    {1, 4, 2431, LD, true, false},
+            {1, 4, 2432, GL, true, false}, {1, 4, 9000, GL, true, false}, {1, 4, 9001, WV, false, true},
+            {1, 8, 0, WV, false, true},    {1, 8, 63, WV, false, true},   {1, 8, 64, LD, true, true},
+            {1, 8, 2431, LD, true, false}, {1, 8, 2432, GL, true, false}, {1, 8, 9000, GL, true, false},
+            {1, 8, 9001, WV, false, true},
+            // the service's LDS-tree sessions keep a shorter table (kLdsSvcNodeRecords)
+            {1, 8, 2351, LD, true, true},  {1, 8, 2352, LD, true, false},
+        };
+        for (const auto &r : rule) {
+            spt::AccelView ac{};
+            ac.tree = r.tree;
+            ac.leaf_slots = r.leaf_slots;
+            ac.n_nodes = r.n_nodes;
+            if (spt::cast_walk(ac) != r.walk || spt::lane_walk_tree(ac) != r.lane || spt::svc_supported(ac) != r.svc) {
+                std::printf("FAIL walk rule tree=%u leaf_slots=%u n_nodes=%u -> walk %u lane %d svc %d\n", r.tree, r.leaf_slots,
+                            r.n_nodes, spt::cast_walk(ac), (int)spt::lane_walk_tree(ac), (int)spt::svc_supported(ac));
+                return 1;
+            }
+        }
     }
     std::printf("ok\n");
     return 0;

@@ -213,6 +213,22 @@ def test_item_orders_are_bijections(tmp_path):
     assert out.returncode == 0 and out.stdout.strip() == "ok", out.stdout
 
 
+def test_staging_plans_match_the_inline_layouts(tmp_path):
+    """The staging plans of the five blocking queries (spt_staging.h: chunk, offsets, total
+    for every combination of optional outputs) against literal values, in
+    tests/cpp/staging_check.cpp: plain g++, AddressSanitizer + UBSan linked into the
+    executable."""
+    import os
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = tmp_path / "staging_check"
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined",
+                    "-I", os.path.join(root, "simplepathtracer_amd", "csrc"),
+                    os.path.join(root, "tests", "cpp", "staging_check.cpp"), "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and out.stdout.strip() == "ok", out.stdout + out.stderr
+
+
 @pytest.mark.parametrize("w,h", [(4, 3), (5, 2), (1, 1), (7, 6)])
 def test_save_bmp_matches_stb_layout(native, tmp_path, w, h):
     """io::SaveImage (IOHelpers.hpp:24-27) calls stbi_write_bmp(path, w, h, 3, g_data);
