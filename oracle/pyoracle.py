@@ -6,7 +6,9 @@ what is pinned against the reference's own code and what is not.
 
 The ref_* functions run the reference's own functions through oracle/_ref/ref_harness
 (`make -C oracle ref`, built where the reference's headers are present), one process and
-one request per call, under a time limit.
+one request per call, under a time limit.  run_dropin_main / run_dropin_driver run the
+reference's application against the drop-in shim (oracle/_ref/ref_dropin_main and
+ref_dropin_driver, same target; they need a GPU), a fresh process per call.
 """
 from __future__ import annotations
 
@@ -386,3 +388,127 @@ def ref_segment(scene: OracleScene, view, eye, yB, yE, xB, xE, seed, task=False)
     taps = np.frombuffer(buf, np.dtype([("index", "<u4"), ("color", "<f4", 4)]), k, 4)
     g = np.frombuffer(buf, np.uint8, REF_WIDTH * REF_HEIGHT * 3, 4 + 20 * k).copy()
     return taps["index"].copy(), taps["color"].copy(), g
+
+
+# ------------------------------------------- the reference's application against the shim
+
+# oracle/_ref/ref_dropin_main is the reference's Main.cpp itself, ref_dropin_driver our
+# driver around its Renderer.hpp (oracle/ref_dropin_driver.cpp); both are built with
+# include/dropin in front of the reference's headers and link libspt_hip.so: they need a GPU.
+DROPIN_MAIN = os.path.join(HERE, "_ref", "ref_dropin_main")
+DROPIN_DRIVER = os.path.join(HERE, "_ref", "ref_dropin_driver")
+DROPIN_TIMEOUT = 300.0  # of tests/test_gpu_parity.py's shim test
+HIP_ILLEGAL_ACCESS = "an illegal memory access was encountered"
+# Set once a child has ended by a signal, run into the time limit or printed HIP's
+# illegal-access error: the tests of tests/test_gpu_dropin_reference.py then skip, so that
+# nothing more is started on a GPU that may have faulted.
+dropin_fault = None
+
+
+class DropinRun:
+    """One child process: its exit status, what it printed, the recorded stbi_write_bmp
+    arguments [(file name, w, h, comp), ...] and the dumped frames (uint8 arrays), in call
+    order."""
+
+    def __init__(self, returncode, output, saves, dumps):
+        self.returncode, self.output, self.saves, self.dumps = returncode, output, saves, dumps
+
+
+def dropin_available() -> bool:
+    return os.path.exists(DROPIN_MAIN) and os.path.exists(DROPIN_DRIVER)
+
+
+def dropin_deps(binary: str):
+    """The prerequisites in the dependency file the compiler left beside a _ref/ binary, as
+    absolute normalised paths; the first is the translation unit.  The file's relative
+    paths are relative to oracle/, where make ran."""
+    with open(binary + ".d") as f:
+        text = f.read().replace("\\\n", " ")
+    return [os.path.normpath(os.path.join(HERE, p)) for p in text.split(":", 1)[1].split()]
+
+
+def dropin_shadowing_errors(binary: str):
+    """What is wrong with a binary's include graph (an empty list: nothing): it must hold the
+    four drop-in headers of this tree and the reference's Renderer.hpp, Globals.hpp,
+    Definitions.hpp, Math.hpp, IOHelpers.hpp and SceneGenerators.hpp, all from one directory
+    outside this tree, and nothing else named like the two tracers or Collision.hpp."""
+    root = os.path.dirname(HERE)
+    deps = dropin_deps(binary)
+    errors = []
+    for rel in ("include/dropin/SingleThreadPathTracer.hpp", "include/dropin/TaskBasedPathTracer.hpp",
+                "include/spt/RenderSegmentShim.hpp", "include/spt_hip.h"):
+        if os.path.join(root, rel) not in deps:
+            errors.append(f"{rel} is not included")
+    ref_dirs = {os.path.dirname(p) for p in deps if os.path.basename(p) == "Renderer.hpp"}
+    if len(ref_dirs) != 1 or next(iter(ref_dirs)).startswith(root + os.sep):
+        return errors + [f"Renderer.hpp comes from {sorted(ref_dirs)}"]
+    ref_dir = next(iter(ref_dirs))
+    for name in ("Globals.hpp", "Definitions.hpp", "Math.hpp", "IOHelpers.hpp", "SceneGenerators.hpp"):
+        if os.path.join(ref_dir, name) not in deps:
+            errors.append(f"the reference's {name} is not included")
+    for name in ("SingleThreadPathTracer.hpp", "TaskBasedPathTracer.hpp", "Collision.hpp"):
+        for p in deps:
+            if os.path.basename(p) == name and not p.startswith(os.path.join(root, "include") + os.sep):
+                errors.append(f"{p} is included: the reference's {name} is not shadowed")
+    return errors
+
+
+def _run_dropin(argv, seed, dump, env, tmp):
+    global dropin_fault
+    dump = dump or os.path.join(tmp, "g_data")
+    e = dict(os.environ)
+    e.update(env or {})
+    e["SPT_REF_CLOCK_SEED"] = str(seed)
+    e["SPT_REF_DUMP"] = dump
+    try:
+        # cwd: the reference opens shaders/ relative to it (absent: empty sources, as headless
+        # GL does not care) and must find no stray file
+        r = subprocess.run(argv, capture_output=True, text=True, errors="replace", timeout=DROPIN_TIMEOUT, env=e, cwd=tmp)
+    except subprocess.TimeoutExpired:
+        dropin_fault = f"{os.path.basename(argv[0])} ran into the {DROPIN_TIMEOUT:.0f} s limit"
+        raise
+    out = r.stdout + r.stderr
+    if r.returncode < 0:
+        dropin_fault = f"{os.path.basename(argv[0])} ended by signal {-r.returncode}"
+    elif HIP_ILLEGAL_ACCESS in out:
+        dropin_fault = f"{os.path.basename(argv[0])} printed HIP's illegal-access error"
+    saves, dumps = [], []
+    k = 1
+    while os.path.exists(f"{dump}.{k}.args"):
+        with open(f"{dump}.{k}.args") as f:
+            name, w, h, comp = f.read().splitlines()
+        saves.append((name, int(w), int(h), int(comp)))
+        dumps.append(np.fromfile(f"{dump}.{k}", np.uint8))
+        k += 1
+    return DropinRun(r.returncode, out, saves, dumps)
+
+
+def run_dropin_main(seed: int, dump=None, env=None) -> DropinRun:
+    """The reference's Main.cpp in a fresh process, its clock reading `seed`.  dump: the path
+    whose .<k> and .<k>.args files the saved frames are left in (default: not kept)."""
+    with tempfile.TemporaryDirectory(prefix="spt_dropin_") as tmp:
+        return _run_dropin([DROPIN_MAIN], seed, dump, env, tmp)
+
+
+def run_dropin_driver(mode: str, scene: str = "random", seed: int = 1, dump=None, env=None, pixels=None, origins=None,
+                      dirs=None):
+    """ref_dropin_driver in a fresh process.  mode "image" or "frames" with scene "init" or
+    "random": the DropinRun.  mode "pick" (the `random` scene): (run, PickSphere of every
+    (x, y) row of pixels, FindClosestIntersectionSpheres of the rays), the two None where
+    the process failed."""
+    with tempfile.TemporaryDirectory(prefix="spt_dropin_") as tmp:
+        if mode != "pick":
+            return _run_dropin([DROPIN_DRIVER, mode, scene], seed, dump, env, tmp)
+        xy = np.ascontiguousarray(pixels, "<u4").reshape(-1, 2)
+        o = np.ascontiguousarray(origins, "<f4").reshape(-1, 4)
+        d = np.ascontiguousarray(dirs, "<f4").reshape(-1, 4)
+        assert len(o) == len(d)
+        req, rsp = os.path.join(tmp, "request"), os.path.join(tmp, "response")
+        with open(req, "wb") as f:
+            f.write(struct.pack("<I", len(xy)) + xy.tobytes() + struct.pack("<I", len(o)) + o.tobytes() + d.tobytes())
+        run = _run_dropin([DROPIN_DRIVER, "pick", req, rsp], seed, dump, env, tmp)
+        if run.returncode != 0 or not os.path.exists(rsp):
+            return run, None, None
+        idx = np.fromfile(rsp, "<u4")
+        assert idx.size == len(xy) + len(o), f"response of {idx.size} indices for {len(xy)} pixels and {len(o)} rays"
+        return run, idx[:len(xy)].copy(), idx[len(xy):].copy()
