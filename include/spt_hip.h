@@ -522,6 +522,69 @@ SPT_API int spt_denoise(spt_ctx *ctx, uint32_t width, uint32_t height, const flo
                         float sigma_color, float sigma_albedo, float sigma_normal, float sigma_depth,
                         uint32_t levels, float *out_rgba /*nullable*/, uint8_t *out_rgb8 /*nullable*/);
 
+/* ---- sample moments: per-pixel mean, second moment and variance of the samples' luminance
+ * Where a frame is still noisy, from the sample words every render leaves on the device.
+ * The call is a SPT_MODE_SEGMENT render of the region: rgba_out and g_data receive exactly
+ * what spt_render_segment writes, bit for bit, and spt_stats counts it as the render it is.
+ * For pixel p, c_s is the colour of sample s as the fold decodes it (the value
+ * spt_render_samples returns).  Everything is fp32, one rounding per operation written, no
+ * contraction; the sums start at +0 and run over s = 0 .. spp - 1 in that order:
+ *   L_s = (c_s.r * 0.2126f + c_s.g * 0.7152f) + c_s.b * 0.0722f
+ *   s1 = s1 + L_s;  s2 = s2 + L_s * L_s
+ *   inv = 1.0f / (float)spp;  m1 = s1 * inv;  m2 = s2 * inv
+ *   d = m2 - m1 * m1;  var = d < 0 ? +0 : d                  (NaN stays NaN)
+ *   mom[p] = {m1, m2, var, (float)spp}                        float4, local pixel order
+ * var is the population variance of the samples' luminance; var / spp is the variance of
+ * the pixel mean, which spt_denoise_var uses.  The sum-of-squares form loses bits where all
+ * samples are nearly equal (m2 and m1 * m1 cancel: var is then 0 or a few ulps of m2, not
+ * the true small variance); spt_denoise_var's var_floor is there for that.
+ * The region has to fit in one sample batch of the workspace (spt_set_workspace), as for
+ * spt_render_samples: SPT_ERR_ARG otherwise, and nothing is rendered.  They need scene,
+ * camera and params (SPT_ERR_STATE otherwise) and use member 0 of a multi-device context.
+ * SPT_ERR_ARG for a null mom, yEnd > height, xEnd > width, an inverted range, strip == 0,
+ * parts == 0 or part >= parts; an empty rectangle is SPT_OK and touches nothing. */
+/* host pointers, blocking; rectangle [yBegin,yEnd) x [xBegin,xEnd) */
+SPT_API int spt_render_moments(spt_ctx *ctx, uint32_t yBegin, uint32_t yEnd, uint32_t xBegin, uint32_t xEnd,
+                               float *rgba_out /*nullable*/, uint8_t *g_data /*nullable*/, float *mom);
+/* device pointers, asynchronous on `stream` (NULL = default stream); the row map and local
+ * pixel order of spt_render_rows_async (d_rgb8: the full frame, g_data layout) */
+SPT_API int spt_render_moments_async(spt_ctx *ctx, uint32_t yBegin, uint32_t yEnd, uint32_t strip, uint32_t parts,
+                                     uint32_t part, uint32_t xBegin, uint32_t xEnd, void *d_rgba /*nullable*/,
+                                     void *d_rgb8 /*nullable*/, void *d_mom, void *stream);
+
+/* ---- variance-guided denoiser: the a-trous filter with its colour term normalised by the
+ * variance of the pixel means (after Schied et al. 2017, SVGF, without the temporal part).
+ * Everything in "denoiser" above holds, with these changes.
+ *   mom  float4 per pixel as spt_render_moments writes it; z = var and w = spp are read.
+ * k_color = 1.0f / (sigma_color * sigma_color) at every level (not scaled by 4^k):
+ * sigma_color counts standard deviations, and the variance shrinks from level to level.
+ * Per pixel once: g_p = mom_p.z / mom_p.w, one IEEE division; a quotient that is not finite
+ * is taken as NaN (an infinite g would leave X finite).  Each level reads (u, g) and
+ * writes (u', g').  For each tap, dc, d_a, d_n and d_z as above, then
+ *   vn = var_floor + (g_p + g_q)
+ *   X  = ((dc * k_color) / vn + d_a * k_albedo) + (d_n * k_normal + d_z * k_depth)
+ *   w  = (h[|i|] * h[|j|]) / (1.0f + X);  if !(w > 0) skip the tap
+ *   acc.c = acc.c + w * u_q.c;  ws = ws + w;  gacc = gacc + (w * w) * g_q
+ * u'_p.c = acc.c / ws and g'_p = gacc / (ws * ws) if ws > 0, else both pass through.
+ * Output: the last level's u' with rgba_p.w in the w lane; out_var (nullable), one float per
+ * pixel: the last level's g'; out_rgb8 as above.  A non-finite colour, feature or g at the
+ * centre makes X NaN: the pixel passes through and its neighbours skip it.
+ * var_floor must be finite and > 0.  Scratch is what spt_denoise_scratch_bytes gives (g
+ * rides in the w lane of the planes).  Argument errors as for spt_denoise, and: a null mom,
+ * a var_floor that is not finite or <= 0, an out_var that overlaps an input, the scratch or
+ * another output, an output that overlaps mom. */
+/* device pointers, asynchronous on `stream` (NULL = default stream) */
+SPT_API int spt_denoise_var_async(spt_ctx *ctx, uint32_t width, uint32_t height, const void *d_rgba, const void *d_feat,
+                                  const void *d_mom, float sigma_color, float sigma_albedo, float sigma_normal,
+                                  float sigma_depth, float var_floor, uint32_t levels, void *d_out_rgba /*nullable*/,
+                                  void *d_out_rgb8 /*nullable*/, void *d_out_var /*nullable*/, void *d_scratch,
+                                  void *stream);
+/* host pointers, blocking; allocates and frees its own device buffers */
+SPT_API int spt_denoise_var(spt_ctx *ctx, uint32_t width, uint32_t height, const float *rgba, const float *feat,
+                            const float *mom, float sigma_color, float sigma_albedo, float sigma_normal,
+                            float sigma_depth, float var_floor, uint32_t levels, float *out_rgba /*nullable*/,
+                            uint8_t *out_rgb8 /*nullable*/, float *out_var /*nullable*/);
+
 SPT_API int spt_get_stats(spt_ctx *ctx, spt_stats *out);
 SPT_API int spt_reset_stats(spt_ctx *ctx);
 

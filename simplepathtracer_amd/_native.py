@@ -156,6 +156,10 @@ def lib() -> ctypes.CDLL:
         "spt_denoise_scratch_bytes": ([u32, u32, u32, P], I),
         "spt_denoise_async": ([P, u32, u32, P, P, f32, f32, f32, f32, u32, P, P, P, P], I),
         "spt_denoise": ([P, u32, u32, P, P, f32, f32, f32, f32, u32, P, P], I),
+        "spt_render_moments": ([P, u32, u32, u32, u32, P, P, P], I),
+        "spt_render_moments_async": ([P, u32, u32, u32, u32, u32, u32, u32, P, P, P, P], I),
+        "spt_denoise_var_async": ([P, u32, u32, P, P, P, f32, f32, f32, f32, f32, u32, P, P, P, P, P], I),
+        "spt_denoise_var": ([P, u32, u32, P, P, P, f32, f32, f32, f32, f32, u32, P, P, P], I),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

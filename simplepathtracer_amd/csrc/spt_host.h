@@ -10,7 +10,8 @@
 //   spt_cast.cpp     ray queries (spt_cast_rays[_async], spt_primary_hits)
 //   spt_trace.cpp    path queries (spt_trace_rays[_async], spt_sample_state)
 //   spt_features.cpp feature buffers (spt_render_features[_async])
-//   spt_denoise.cpp  the denoiser (spt_denoise[_async])
+//   spt_denoise.cpp  the denoiser (spt_denoise[_async], spt_denoise_var[_async])
+//   spt_moments.cpp  per-pixel sample moments (spt_render_moments[_async])
 //   spt_staging.cpp  the device staging of their blocking forms; spt_staging.h is its
 //                    HIP-free half (the plan: chunk size, offsets, total)
 // The context owns the device copy of the reference's global state (scene SoA, camera,
@@ -223,8 +224,9 @@ struct SvcJobSpec {
     uint64_t slot_local;
 };
 // Render the rows of `map` and fold them into d_rgba (local pixel order) and/or
-// d_rgb8 (full frame).  keep_samples: leave the per-sample colours of a single
-// batch in d_samples (debug path).
+// d_rgb8 (full frame).  keep_samples: one sample batch, launched on `s` (no service job, no
+// companion stream), its sample words left in the stream's d_samples; folded only where an
+// output is given (spt_render_samples gives none, spt_render_moments its caller's).
 // Progressive rendering: batches of at most pass_spp samples, outputs written after
 // every batch and after_pass(samples done) called (nonzero return: stop early).
 struct Progress {

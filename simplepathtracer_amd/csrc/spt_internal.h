@@ -667,4 +667,27 @@ struct DenoiseArgs {
 };
 hipError_t launch_denoise_level(const DenoiseArgs &a, hipStream_t s);
 
+// One level of the variance-guided filter (spt_denoise_var[_async]): `in` is the caller's
+// rgba at level 0 (g worked out from mom as the cell is staged), then the previous level's
+// plane with g in its w lane.  Intermediate levels write {u', g'} to out; the last level
+// (rgba non-null: the caller's input, for its w lane) writes {u', rgba.w} to out, g' to
+// out_var and the bytes to rgb8, each nullable.  kc is 1 / sigma_color^2 at every level.
+struct DenoiseVarArgs {
+    const float4 *in, *feat, *mom, *rgba;
+    float4 *out;
+    float *out_var;
+    uint8_t *rgb8;
+    uint32_t width, height;
+    uint32_t step, sx, sy, tiles_x, tiles_y;  // as DenoiseArgs
+    uint32_t first;                           // level 0
+    float kc, ka, kn, kz, var_floor;
+};
+hipError_t launch_denoise_var_level(const DenoiseVarArgs &a, hipStream_t s);
+
+// ---- sample moments (spt_moments.hip; spt_render_moments[_async]) ----------------------
+// Per pixel of a single-batch SPT_MODE_SEGMENT region whose sample words lie in f.samples
+// (f.map, f.npix, f.spp_batch = spp; the decode tables of fold_args): mom[p] = {m1, m2, var,
+// spp} of the samples' luminance in sample order, p the local row-major pixel.
+hipError_t launch_moments(const FoldArgs &f, float4 *mom, hipStream_t s);
+
 }  // namespace spt

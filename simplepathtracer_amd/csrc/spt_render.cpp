@@ -52,7 +52,7 @@ int render_impl(spt_ctx *ctx, int mode, const spt::RowMap &map, float4 *d_rgba, 
     uint32_t spp_batch = (uint32_t)std::min<uint64_t>(ctx->spp, per);
     if (pg) spp_batch = std::min(spp_batch, std::max(pg->pass_spp, 1u));
     if (keep_samples && spp_batch != ctx->spp)
-        return fail(ctx, SPT_ERR_ARG, "region * spp exceeds the workspace for spt_render_samples");
+        return fail(ctx, SPT_ERR_ARG, "region * spp exceeds the workspace for spt_render_samples / spt_render_moments");
     const uint64_t items_max = (uint64_t)npix * spp_batch;
     // the resident render service takes the launch when it is on and can (svc_eligible);
     // a launch it cannot take ends the session first, so that launch has the whole GPU
@@ -202,7 +202,9 @@ int render_impl(spt_ctx *ctx, int mode, const spt::RowMap &map, float4 *d_rgba, 
         }
         ctx->pending_render.push_back(ev);
         ctx->launches++;
-        if (keep_samples) continue;
+        // kept samples without outputs (spt_render_samples) need no fold; with outputs
+        // (spt_render_moments) the one batch is folded as any render's
+        if (keep_samples && !d_rgba && !d_rgb8) continue;
         fa.spp_batch = b;
         fa.first = s0 == 0;
         fa.last = s0 + b >= ctx->spp;

@@ -1,7 +1,8 @@
 // spt_staging.h -- device staging of the blocking queries (spt_cast_rays, spt_primary_hits,
-// spt_trace_rays, spt_render_features, spt_denoise): one device allocation cut into the
-// arrays of a chunk of the call's items (rays, rows of pixels, or the whole image), which
-// the call copies in, launches over and copies out chunk by chunk.  The plan -- chunk size,
+// spt_trace_rays, spt_render_features, spt_denoise, spt_denoise_var, spt_render_moments): one
+// device allocation cut into the arrays of a chunk of the call's items (rays, rows of
+// pixels, or the whole image), which the call copies in, launches over and copies out chunk
+// by chunk.  The plan -- chunk size,
 // offsets, total -- is HIP-free (standard headers only: tests/cpp/staging_check.cpp drives
 // it on the CPU); Staging, the allocation itself, is spt_staging.cpp.
 #pragma once
@@ -51,7 +52,7 @@ inline StagingPlan staging_plan(const StagingArray *arrays, int n_arrays, size_t
     return p;
 }
 
-// The five blocking forms' arrays, in the order their Staging::at() indices name them.
+// The blocking forms' arrays, in the order their Staging::at() indices name them.
 // spt_cast_rays, per ray: origin, direction in; index (+ hit record: two float4) out
 inline StagingPlan cast_rays_plan(size_t n, bool hit)
 {
@@ -82,6 +83,19 @@ inline StagingPlan denoise_plan(size_t npix, size_t planes, bool out, bool rgb8)
 {
     const StagingArray a[5] = {{16}, {32}, {16, out}, {planes * 16, planes != 0}, {3, rgb8, true}};
     return staging_plan(a, 5, npix, StagingItems::kAll);
+}
+// spt_denoise_var beside denoise_plan's arrays, per pixel: mom in; out_var out
+inline StagingPlan denoise_var_plan(size_t npix, bool out_var)
+{
+    const StagingArray a[2] = {{16}, {4, out_var}};
+    return staging_plan(a, 2, npix, StagingItems::kAll);
+}
+// spt_render_moments, the whole region as one item: rgba out, mom out, then the frame's
+// g_data bytes (the fold writes the region's band of a full frame)
+inline StagingPlan moments_plan(size_t npix, size_t frame_bytes, bool rgba, bool g_data)
+{
+    const StagingArray a[3] = {{npix * 16, rgba}, {npix * 16}, {frame_bytes, g_data, true}};
+    return staging_plan(a, 3, 1, StagingItems::kAll);
 }
 
 // The allocation of a plan, for one blocking call on one stream (spt_staging.cpp).  A call

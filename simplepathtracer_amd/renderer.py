@@ -346,15 +346,9 @@ class Context:
         return {"albedo": feat[:, :, 0, :3], "coverage": feat[:, :, 0, 3], "normal": feat[:, :, 1, :3],
                 "depth": feat[:, :, 1, 3], "ids": idx.reshape(h, w)}
 
-    def denoise(self, rgba, feat, sigma_color=30.0, sigma_albedo=0.1, sigma_normal=0.25, sigma_depth=0.5, levels=3,
-                g_data=False):
-        """The edge-avoiding a-trous filter of include/spt_hip.h "denoiser" on the device
-        (spt_denoise).  rgba: an (H, W, 4) float array, colours on the renders' 0..255 scale,
-        or the current frame as (W * H, 4) (what render_frame returns).  feat: what
-        render_features returns for the same pixels ((pixels, 2, 4), or any shape of 8 floats
-        per pixel), or the dict of feature_buffers().  Each sigma must be > 0 (inf switches
-        its term off); levels is 1..8.  Returns the filtered image in rgba's shape, or with
-        g_data=True (image, bytes): bytes the image as a g_data frame of its own W x H."""
+    def _denoise_inputs(self, rgba, feat):
+        """(rgba, feat, w, h) of denoise's and denoise_variance's image arguments, as
+        contiguous float32 arrays."""
         rgba = np.ascontiguousarray(rgba, np.float32)
         if rgba.ndim == 3 and rgba.shape[2] == 4:
             h, w = rgba.shape[:2]
@@ -371,6 +365,18 @@ class Context:
         feat = np.ascontiguousarray(feat, np.float32)
         if feat.size != w * h * 8:
             raise ValueError(f"feat: expected 8 floats for each of {w} x {h} pixels, got shape {feat.shape}")
+        return rgba, feat, w, h
+
+    def denoise(self, rgba, feat, sigma_color=30.0, sigma_albedo=0.1, sigma_normal=0.25, sigma_depth=0.5, levels=3,
+                g_data=False):
+        """The edge-avoiding a-trous filter of include/spt_hip.h "denoiser" on the device
+        (spt_denoise).  rgba: an (H, W, 4) float array, colours on the renders' 0..255 scale,
+        or the current frame as (W * H, 4) (what render_frame returns).  feat: what
+        render_features returns for the same pixels ((pixels, 2, 4), or any shape of 8 floats
+        per pixel), or the dict of feature_buffers().  Each sigma must be > 0 (inf switches
+        its term off); levels is 1..8.  Returns the filtered image in rgba's shape, or with
+        g_data=True (image, bytes): bytes the image as a g_data frame of its own W x H."""
+        rgba, feat, w, h = self._denoise_inputs(rgba, feat)
         out = np.zeros_like(rgba)
         g = np.zeros(w * h * 3, np.uint8) if g_data else None
         self._check(_native.lib().spt_denoise(self._h, w, h, _p(rgba), _p(feat), sigma_color, sigma_albedo, sigma_normal,
@@ -390,13 +396,77 @@ class Context:
                                                     ctypes.c_void_p(d_out or None), ctypes.c_void_p(d_rgb8 or None),
                                                     ctypes.c_void_p(d_scratch or None), ctypes.c_void_p(stream or None)))
 
-    def render_denoised(self, **sigmas) -> np.ndarray:
+    def render_moments(self, yB, yE, xB, xE, g_data=None, rgba=True):
+        """A segment-mode render of the rectangle that also returns its per-pixel sample
+        moments (spt_render_moments): (rgba, mom), rgba what render_segment returns (None with
+        rgba=False), mom of shape (pixels, 4), float32: the mean and the second moment of the
+        samples' luminance, their population variance and the sample count.  Writes g_data
+        bytes of the region if given.  The region's samples must fit the workspace at once."""
+        n = max(yE - yB, 0) * max(xE - xB, 0)
+        out = np.zeros((n, 4), np.float32) if rgba else None
+        mom = np.zeros((n, 4), np.float32)
+        gp = None
+        if g_data is not None:
+            assert g_data.dtype == np.uint8 and g_data.flags.c_contiguous
+            gp = _p(g_data)
+        self._check(_native.lib().spt_render_moments(self._h, yB, yE, xB, xE, _p(out) if rgba else None, gp, _p(mom)))
+        return out, mom
+
+    def render_moments_async(self, yB, yE, strip, parts, part, xB, xE, d_rgba=0, d_rgb8=0, d_mom=0, stream=0) -> None:
+        """Device-resident render_moments (spt_render_moments_async) over the rows of
+        render_rows_async's row map: raw device pointers to the float4 colours and / or the
+        frame's g_data bytes, and to one float4 of moments per local pixel, enqueued on
+        `stream` (a hipStream_t; 0 = the default stream)."""
+        self._check(_native.lib().spt_render_moments_async(self._h, yB, yE, strip, parts, part, xB, xE,
+                                                           ctypes.c_void_p(d_rgba or None),
+                                                           ctypes.c_void_p(d_rgb8 or None),
+                                                           ctypes.c_void_p(d_mom or None),
+                                                           ctypes.c_void_p(stream or None)))
+
+    def denoise_variance(self, rgba, feat, mom, sigma_color=4.0, sigma_albedo=0.1, sigma_normal=0.25, sigma_depth=0.5,
+                         var_floor=1.0, levels=3, g_data=False, variance=False):
+        """The variance-guided a-trous filter of include/spt_hip.h "variance-guided denoiser"
+        on the device (spt_denoise_var): denoise's arguments, mom what render_moments returns
+        for the same pixels (4 floats per pixel), and var_floor, finite and > 0, added to the
+        variances that normalise the colour term; sigma_color counts standard deviations.
+        Returns the filtered image in rgba's shape; with g_data and / or variance a tuple
+        (image[, bytes][, var]), var the filtered variance of the pixel means, (H, W)."""
+        rgba, feat, w, h = self._denoise_inputs(rgba, feat)
+        mom = np.ascontiguousarray(mom, np.float32)
+        if mom.size != w * h * 4:
+            raise ValueError(f"mom: expected 4 floats for each of {w} x {h} pixels, got shape {mom.shape}")
+        out = np.zeros_like(rgba)
+        g = np.zeros(w * h * 3, np.uint8) if g_data else None
+        var = np.zeros((h, w), np.float32) if variance else None
+        self._check(_native.lib().spt_denoise_var(self._h, w, h, _p(rgba), _p(feat), _p(mom), sigma_color, sigma_albedo,
+                                                  sigma_normal, sigma_depth, var_floor, int(levels), _p(out),
+                                                  _p(g) if g_data else None, _p(var) if variance else None))
+        res = (out,) + ((g,) if g_data else ()) + ((var,) if variance else ())
+        return res if len(res) > 1 else out
+
+    def denoise_variance_async(self, width, height, d_rgba, d_feat, d_mom, sigma_color=4.0, sigma_albedo=0.1,
+                               sigma_normal=0.25, sigma_depth=0.5, var_floor=1.0, levels=3, d_out=0, d_rgb8=0, d_out_var=0,
+                               d_scratch=0, stream=0) -> None:
+        """Device-resident denoise_variance (spt_denoise_var_async): denoise_async's pointers,
+        d_mom (one float4 per pixel) and d_out_var (one float per pixel, optional)."""
+        self._check(_native.lib().spt_denoise_var_async(
+            self._h, int(width), int(height), ctypes.c_void_p(d_rgba or None), ctypes.c_void_p(d_feat or None),
+            ctypes.c_void_p(d_mom or None), sigma_color, sigma_albedo, sigma_normal, sigma_depth, var_floor, int(levels),
+            ctypes.c_void_p(d_out or None), ctypes.c_void_p(d_rgb8 or None), ctypes.c_void_p(d_out_var or None),
+            ctypes.c_void_p(d_scratch or None), ctypes.c_void_p(stream or None)))
+
+    def render_denoised(self, variance=False, **sigmas) -> np.ndarray:
         """The current frame rendered, its feature buffers, and the frame filtered by denoise
         (whose keyword arguments `sigmas` takes): render_frame + feature_buffers + denoise.
-        Returns the (H, W, 4) float image, or what denoise returns with g_data=True."""
+        Returns the (H, W, 4) float image, or what denoise returns with g_data=True.
+        With variance=True the variance-guided filter instead: render_moments of the whole
+        frame + feature_buffers + denoise_variance (whose keyword arguments `sigmas` takes)."""
         if self._frame is None:
             raise _native.SptError(2, "params not set (set_params)")
         w, h = self._frame
+        if variance:
+            rgba, mom = self.render_moments(0, h, 0, w)
+            return self.denoise_variance(rgba.reshape(h, w, 4), self.feature_buffers(), mom, **sigmas)
         return self.denoise(self.render_frame().reshape(h, w, 4), self.feature_buffers(), **sigmas)
 
     def synchronize(self) -> None:
