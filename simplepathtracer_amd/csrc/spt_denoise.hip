@@ -1,7 +1,9 @@
 // spt_denoise.hip -- the edge-avoiding a-trous filter guided by the feature buffers:
 // spt_denoise[_async] (spt_denoise.cpp; the definition is include/spt_hip.h "denoiser",
-// DESIGN.md §4.11), and its variance-guided variant spt_denoise_var[_async] (the kernel at
-// the end of the file; "variance-guided denoiser").
+// DESIGN.md §4.11), and its variance-guided variant spt_denoise_var[_async] ("variance-guided
+// denoiser").  Both are one level body, denoise_level<kVar>: what the
+// variance-guided form adds stands under `if constexpr (kVar)`, and denoise_level_kernel and
+// denoise_var_level_kernel are its two instantiations.
 //
 // One launch per level.  Level k has step s = 2^k, and the 25 taps of a pixel all lie on the
 // lattice of pixels congruent to it modulo s in x and in y.  A block of 256 threads takes a
@@ -44,11 +46,15 @@ __device__ __forceinline__ uint32_t xcd_run_block(uint32_t b, uint32_t n)
     return first + j;
 }
 
-}  // namespace
-
-__global__ __launch_bounds__(kDenoiseBlock) void denoise_level_kernel(DenoiseArgs a)
+// One level, both forms.  kVar, the variance-guided form (spt_denoise_var):
+// g, the variance of the pixel mean, rides in s_u's w lane -- level 0 works it out as the
+// cell is staged (mom.z / mom.w, as z), later levels find it in the plane the previous level
+// wrote -- the colour term is divided by var_floor + (g_p + g_q), two IEEE divisions per tap,
+// and the last level takes the output's w lane from the caller's rgba.
+template <bool kVar>
+__device__ __forceinline__ void denoise_level(const DenoiseArgs &a)
 {
-    __shared__ float4 s_u[kCells * kCells];  // u.rgb, w = the pixel's own w lane
+    __shared__ float4 s_u[kCells * kCells];  // u.rgb, w = the pixel's own w lane (kVar: g)
     __shared__ float4 s_a[kCells * kCells];  // alb.rgb, w = 1 inside the image, 0 outside
     __shared__ float4 s_n[kCells * kCells];  // nrm.xyz, z
 
@@ -71,6 +77,13 @@ __global__ __launch_bounds__(kDenoiseBlock) void denoise_level_kernel(DenoiseArg
         if (lx >= 0 && ly >= 0 && x < (int64_t)a.width && y < (int64_t)a.height) {
             const size_t p = (size_t)y * a.width + (size_t)x;
             u = a.in[p];
+            if constexpr (kVar) {
+                if (a.first) {
+                    const float4 m = a.mom[p];
+                    const float g = m.z / m.w;
+                    u.w = __builtin_isfinite(g) ? g : __builtin_nanf("");  // +-inf would not make X NaN
+                }
+            }
             al = a.feat[2u * p];
             nz = a.feat[2u * p + 1u];
             const float cov = al.w;
@@ -89,6 +102,7 @@ __global__ __launch_bounds__(kDenoiseBlock) void denoise_level_kernel(DenoiseArg
     const uint32_t cc = (j + kHalo) * kCells + (i + kHalo);
     const float4 up = s_u[cc], ap = s_a[cc], np = s_n[cc];
     float acc_r = 0.0f, acc_g = 0.0f, acc_b = 0.0f, ws = 0.0f;
+    [[maybe_unused]] float gacc = 0.0f;
     const float h[3] = {0.375f, 0.25f, 0.0625f};
 #pragma unroll
     for (int dj = -2; dj <= 2; ++dj) {
@@ -104,7 +118,12 @@ __global__ __launch_bounds__(kDenoiseBlock) void denoise_level_kernel(DenoiseArg
             const float d_n = (dn_x * dn_x + dn_y * dn_y) + dn_z * dn_z;
             const float dz = nq.w - np.w;
             const float d_z = dz * dz;
-            const float X = (dc * a.kc + d_a * a.ka) + (d_n * a.kn + d_z * a.kz);
+            float tc = dc * a.kc;
+            if constexpr (kVar) {
+                const float vn = a.var_floor + (up.w + uq.w);
+                tc = tc / vn;
+            }
+            const float X = (tc + d_a * a.ka) + (d_n * a.kn + d_z * a.kz);
             const float w = (h[di < 0 ? -di : di] * h[dj < 0 ? -dj : dj]) / (1.0f + X);
             // a cell outside the image, a NaN and a zero weight all skip the tap
             if (aq.w != 0.0f && w > 0.0f) {
@@ -112,17 +131,26 @@ __global__ __launch_bounds__(kDenoiseBlock) void denoise_level_kernel(DenoiseArg
                 acc_g = acc_g + w * uq.y;
                 acc_b = acc_b + w * uq.z;
                 ws = ws + w;
+                if constexpr (kVar) gacc = gacc + (w * w) * uq.w;
             }
         }
     }
-    float4 o = up;  // no weight at all: the pixel passes through, bits and all
+    float4 o = up;  // no weight at all: the pixel (kVar: and g) passes through, bits and all
     if (ws > 0.0f) {
         o.x = acc_r / ws;
         o.y = acc_g / ws;
         o.z = acc_b / ws;
+        if constexpr (kVar) o.w = gacc / (ws * ws);
     }
     const uint32_t x = rx + a.step * lx, y = ry + a.step * ly;
-    if (a.out) a.out[(size_t)y * a.width + x] = o;
+    const size_t p = (size_t)y * a.width + x;
+    if constexpr (kVar) {
+        if (a.rgba) {  // the last level
+            if (a.out_var) a.out_var[p] = o.w;
+            o.w = a.rgba[p].w;
+        }
+    }
+    if (a.out) a.out[p] = o;
     if (a.rgb8) {
         // io::WritePixel's place in a g_data frame of the image's own size
         uint8_t *g = a.rgb8 + (size_t)3 * ((size_t)(a.height - 1u - y) * a.width + x);
@@ -132,123 +160,18 @@ __global__ __launch_bounds__(kDenoiseBlock) void denoise_level_kernel(DenoiseArg
     }
 }
 
-hipError_t launch_denoise_level(const DenoiseArgs &a, hipStream_t s)
+}  // namespace
+
+// the two forms under the names that profiles and DESIGN.md §4.11 / §4.12 use
+__global__ __launch_bounds__(kDenoiseBlock) void denoise_level_kernel(DenoiseArgs a) { denoise_level<false>(a); }
+__global__ __launch_bounds__(kDenoiseBlock) void denoise_var_level_kernel(DenoiseArgs a) { denoise_level<true>(a); }
+
+hipError_t launch_denoise_level(const DenoiseArgs &a, bool var, hipStream_t s)
 {
     const uint64_t blocks = (uint64_t)a.sx * a.tiles_x * a.sy * a.tiles_y;
     if (blocks == 0) return hipSuccess;
     if (blocks > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
-    hipLaunchKernelGGL(denoise_level_kernel, dim3((uint32_t)blocks), dim3(kDenoiseBlock), 0, s, a);
-    return hipGetLastError();
-}
-
-// The variance-guided level (spt_denoise_var): denoise_level_kernel's
-// shape -- the same tiles, block order and three LDS planes -- written beside it, so that
-// kernel's code is untouched.  g, the variance of the pixel mean, rides in s_u's w lane:
-// level 0 works it out as the cell is staged (mom.z / mom.w, as z), later levels find it in
-// the plane the previous level wrote.  Two IEEE divisions per tap.  The last level takes the
-// output's w lane from the caller's rgba.
-__global__ __launch_bounds__(kDenoiseBlock) void denoise_var_level_kernel(DenoiseVarArgs a)
-{
-    __shared__ float4 s_u[kCells * kCells];  // u.rgb, w = g
-    __shared__ float4 s_a[kCells * kCells];  // alb.rgb, w = 1 inside the image, 0 outside
-    __shared__ float4 s_n[kCells * kCells];  // nrm.xyz, z
-
-    uint32_t l = xcd_run_block(blockIdx.x, gridDim.x);
-    const uint32_t rx = l % a.sx;
-    l /= a.sx;
-    const uint32_t tx = l % a.tiles_x;
-    l /= a.tiles_x;
-    const uint32_t ry = l % a.sy, ty = l / a.sy;
-    const uint32_t lw = (a.width - rx + a.step - 1u) / a.step, lh = (a.height - ry + a.step - 1u) / a.step;
-    if (tx * kTile >= lw || ty * kTile >= lh) return;  // the whole block
-
-    for (uint32_t c = threadIdx.x; c < kCells * kCells; c += kDenoiseBlock) {
-        const uint32_t cy = c / kCells, cx = c - cy * kCells;
-        const int64_t lx = (int64_t)(tx * kTile + cx) - kHalo, ly = (int64_t)(ty * kTile + cy) - kHalo;
-        const int64_t x = (int64_t)rx + lx * (int64_t)a.step, y = (int64_t)ry + ly * (int64_t)a.step;
-        float4 u = make_float4(0.f, 0.f, 0.f, 0.f), al = u, nz = u;
-        if (lx >= 0 && ly >= 0 && x < (int64_t)a.width && y < (int64_t)a.height) {
-            const size_t p = (size_t)y * a.width + (size_t)x;
-            u = a.in[p];
-            if (a.first) {
-                const float4 m = a.mom[p];
-                const float g = m.z / m.w;
-                u.w = __builtin_isfinite(g) ? g : __builtin_nanf("");  // +-inf would not make X NaN
-            }
-            al = a.feat[2u * p];
-            nz = a.feat[2u * p + 1u];
-            const float cov = al.w;
-            nz.w = cov > 0.0f ? nz.w / cov : 0.0f;
-            al.w = 1.0f;
-        }
-        s_u[c] = u;
-        s_a[c] = al;
-        s_n[c] = nz;
-    }
-    __syncthreads();
-
-    const uint32_t i = threadIdx.x & (kTile - 1u), j = threadIdx.x >> 4;
-    const uint32_t lx = tx * kTile + i, ly = ty * kTile + j;
-    if (lx >= lw || ly >= lh) return;  // past the image
-    const uint32_t cc = (j + kHalo) * kCells + (i + kHalo);
-    const float4 up = s_u[cc], ap = s_a[cc], np = s_n[cc];
-    float acc_r = 0.0f, acc_g = 0.0f, acc_b = 0.0f, ws = 0.0f, gacc = 0.0f;
-    const float h[3] = {0.375f, 0.25f, 0.0625f};
-#pragma unroll
-    for (int dj = -2; dj <= 2; ++dj) {
-#pragma unroll
-        for (int di = -2; di <= 2; ++di) {
-            const uint32_t q = (uint32_t)((int)cc + dj * (int)kCells + di);
-            const float4 uq = s_u[q], aq = s_a[q], nq = s_n[q];
-            const float du_r = uq.x - up.x, du_g = uq.y - up.y, du_b = uq.z - up.z;
-            const float dc = (du_r * du_r + du_g * du_g) + du_b * du_b;
-            const float da_r = aq.x - ap.x, da_g = aq.y - ap.y, da_b = aq.z - ap.z;
-            const float d_a = (da_r * da_r + da_g * da_g) + da_b * da_b;
-            const float dn_x = nq.x - np.x, dn_y = nq.y - np.y, dn_z = nq.z - np.z;
-            const float d_n = (dn_x * dn_x + dn_y * dn_y) + dn_z * dn_z;
-            const float dz = nq.w - np.w;
-            const float d_z = dz * dz;
-            const float vn = a.var_floor + (up.w + uq.w);
-            const float X = ((dc * a.kc) / vn + d_a * a.ka) + (d_n * a.kn + d_z * a.kz);
-            const float w = (h[di < 0 ? -di : di] * h[dj < 0 ? -dj : dj]) / (1.0f + X);
-            // a cell outside the image, a NaN and a zero weight all skip the tap
-            if (aq.w != 0.0f && w > 0.0f) {
-                acc_r = acc_r + w * uq.x;
-                acc_g = acc_g + w * uq.y;
-                acc_b = acc_b + w * uq.z;
-                ws = ws + w;
-                gacc = gacc + (w * w) * uq.w;
-            }
-        }
-    }
-    float4 o = up;  // no weight at all: colour and g pass through, bits and all
-    if (ws > 0.0f) {
-        o.x = acc_r / ws;
-        o.y = acc_g / ws;
-        o.z = acc_b / ws;
-        o.w = gacc / (ws * ws);
-    }
-    const uint32_t x = rx + a.step * lx, y = ry + a.step * ly;
-    const size_t p = (size_t)y * a.width + x;
-    if (a.rgba) {  // the last level
-        if (a.out_var) a.out_var[p] = o.w;
-        o.w = a.rgba[p].w;
-    }
-    if (a.out) a.out[p] = o;
-    if (a.rgb8) {
-        uint8_t *g = a.rgb8 + (size_t)3 * ((size_t)(a.height - 1u - y) * a.width + x);
-        g[0] = gamma_byte(o.x);
-        g[1] = gamma_byte(o.y);
-        g[2] = gamma_byte(o.z);
-    }
-}
-
-hipError_t launch_denoise_var_level(const DenoiseVarArgs &a, hipStream_t s)
-{
-    const uint64_t blocks = (uint64_t)a.sx * a.tiles_x * a.sy * a.tiles_y;
-    if (blocks == 0) return hipSuccess;
-    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
-    hipLaunchKernelGGL(denoise_var_level_kernel, dim3((uint32_t)blocks), dim3(kDenoiseBlock), 0, s, a);
+    hipLaunchKernelGGL(var ? denoise_var_level_kernel : denoise_level_kernel, dim3((uint32_t)blocks), dim3(kDenoiseBlock), 0, s, a);
     return hipGetLastError();
 }
 

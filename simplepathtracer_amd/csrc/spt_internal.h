@@ -650,11 +650,18 @@ struct FeatArgs {
 };
 hipError_t launch_features(const RenderArgs &k, const FeatArgs &f, hipStream_t s);
 
-// ---- denoiser (spt_denoise.hip; spt_denoise[_async]) -----------------------------------
+// ---- denoiser (spt_denoise.hip; spt_denoise[_async], spt_denoise_var[_async]) ----------
 // One level of the a-trous filter over a width x height image: reads `in` (level 0: the
 // caller's rgba, then the previous level's output) and feat, writes out (nullable) and / or
-// the g_data bytes rgb8 (nullable, last level only).  The four factors are 1 / sigma^2, kc
-// already times 4^level.
+// the g_data bytes rgb8 (nullable, last level only).  The four factors are 1 / sigma^2; the
+// plain form's kc is already times 4^level, the variance-guided form's is the same at every
+// level.
+//
+// The fields after kz are the variance-guided form's (`var`): denoise_level_kernel reads
+// none of them.  There `in` is the caller's rgba at level 0 (first: g is worked out from mom
+// as the cell is staged), then the previous level's plane with g in its w lane.
+// Intermediate levels write {u', g'} to out; the last level (rgba non-null: the caller's
+// input, for its w lane) writes {u', rgba.w} to out and g' to out_var (nullable).
 struct DenoiseArgs {
     const float4 *in, *feat;
     float4 *out;
@@ -664,25 +671,12 @@ struct DenoiseArgs {
     uint32_t sx, sy;            // lattices with a pixel: min(step, width), min(step, height)
     uint32_t tiles_x, tiles_y;  // 16x16 tiles of the longest lattice: ceil(ceil(width / step) / 16), ...
     float kc, ka, kn, kz;
-};
-hipError_t launch_denoise_level(const DenoiseArgs &a, hipStream_t s);
-
-// One level of the variance-guided filter (spt_denoise_var[_async]): `in` is the caller's
-// rgba at level 0 (g worked out from mom as the cell is staged), then the previous level's
-// plane with g in its w lane.  Intermediate levels write {u', g'} to out; the last level
-// (rgba non-null: the caller's input, for its w lane) writes {u', rgba.w} to out, g' to
-// out_var and the bytes to rgb8, each nullable.  kc is 1 / sigma_color^2 at every level.
-struct DenoiseVarArgs {
-    const float4 *in, *feat, *mom, *rgba;
-    float4 *out;
+    float var_floor;
+    uint32_t first;  // level 0
+    const float4 *mom, *rgba;
     float *out_var;
-    uint8_t *rgb8;
-    uint32_t width, height;
-    uint32_t step, sx, sy, tiles_x, tiles_y;  // as DenoiseArgs
-    uint32_t first;                           // level 0
-    float kc, ka, kn, kz, var_floor;
 };
-hipError_t launch_denoise_var_level(const DenoiseVarArgs &a, hipStream_t s);
+hipError_t launch_denoise_level(const DenoiseArgs &a, bool var, hipStream_t s);
 
 // ---- sample moments (spt_moments.hip; spt_render_moments[_async]) ----------------------
 // Per pixel of a single-batch SPT_MODE_SEGMENT region whose sample words lie in f.samples

@@ -2,9 +2,10 @@
 // spt_trace_rays, spt_render_features, spt_denoise, spt_denoise_var, spt_render_moments): one
 // device allocation cut into the arrays of a chunk of the call's items (rays, rows of
 // pixels, or the whole image), which the call copies in, launches over and copies out chunk
-// by chunk.  The plan -- chunk size,
-// offsets, total -- is HIP-free (standard headers only: tests/cpp/staging_check.cpp drives
-// it on the CPU); Staging, the allocation itself, is spt_staging.cpp.
+// by chunk.  One plan per form (the two filters share denoise_plan: the variance-guided one
+// has two more arrays present).  The plan -- chunk size, offsets, total -- is HIP-free
+// (standard headers only: tests/cpp/staging_check.cpp drives it on the CPU); Staging, the
+// allocation itself, is spt_staging.cpp.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -29,7 +30,7 @@ struct StagingArray {
     bool present = true, exact = false;
 };
 enum class StagingItems { kRays, kRows, kAll };  // chunks of cast_chunk, of band_chunk, or one chunk
-constexpr int kStagingMaxArrays = 5;
+constexpr int kStagingMaxArrays = 7;
 struct StagingPlan {
     size_t chunk = 0;  // items per chunk, at most the call's
     size_t total = 0;  // bytes to allocate
@@ -77,18 +78,13 @@ inline StagingPlan features_plan(size_t w, size_t h, bool feat, bool ids)
     const StagingArray a[2] = {{w * 32, feat}, {w * 4, ids}};
     return staging_plan(a, 2, h, StagingItems::kRows);
 }
-// spt_denoise, per pixel of the whole image: rgba, feat in; out_rgba, the ping-pong planes
-// between levels, then the g_data bytes
-inline StagingPlan denoise_plan(size_t npix, size_t planes, bool out, bool rgb8)
+// spt_denoise and spt_denoise_var, per pixel of the whole image: rgba, feat in; out_rgba,
+// the ping-pong planes between levels; the variance-guided form's mom in and out_var out
+// (both absent for spt_denoise); then the g_data bytes
+inline StagingPlan denoise_plan(size_t npix, size_t planes, bool out, bool rgb8, bool mom = false, bool out_var = false)
 {
-    const StagingArray a[5] = {{16}, {32}, {16, out}, {planes * 16, planes != 0}, {3, rgb8, true}};
-    return staging_plan(a, 5, npix, StagingItems::kAll);
-}
-// spt_denoise_var beside denoise_plan's arrays, per pixel: mom in; out_var out
-inline StagingPlan denoise_var_plan(size_t npix, bool out_var)
-{
-    const StagingArray a[2] = {{16}, {4, out_var}};
-    return staging_plan(a, 2, npix, StagingItems::kAll);
+    const StagingArray a[7] = {{16}, {32}, {16, out}, {planes * 16, planes != 0}, {16, mom}, {4, out_var}, {3, rgb8, true}};
+    return staging_plan(a, 7, npix, StagingItems::kAll);
 }
 // spt_render_moments, the whole region as one item: rgba out, mom out, then the frame's
 // g_data bytes (the fold writes the region's band of a full frame)

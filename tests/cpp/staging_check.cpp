@@ -51,25 +51,36 @@ const Case kCases[] = {
     {P(features_plan(3, 5, true, true)), 5, {0, 480}, 544},
     {P(features_plan(3, 5, true, false)), 5, {0, X}, 480},
     {P(features_plan(3, 5, false, true)), 5, {X, 0}, 64},
-    // spt_denoise(npix, planes = min(levels - 1, 2), out_rgba, out_rgb8): 1201 x 801, 5 x 3
-    {P(denoise_plan(962001, 0, true, true)), 962001, {0, 15392016, 46176048, X, 61568064}, 64454067},
-    {P(denoise_plan(962001, 0, true, false)), 962001, {0, 15392016, 46176048, X, X}, 61568064},
-    {P(denoise_plan(962001, 0, false, true)), 962001, {0, 15392016, X, X, 46176048}, 49062051},
-    {P(denoise_plan(962001, 1, true, true)), 962001, {0, 15392016, 46176048, 61568064, 76960080}, 79846083},
-    {P(denoise_plan(962001, 1, true, false)), 962001, {0, 15392016, 46176048, 61568064, X}, 76960080},
-    {P(denoise_plan(962001, 1, false, true)), 962001, {0, 15392016, X, 46176048, 61568064}, 64454067},
-    {P(denoise_plan(962001, 2, true, true)), 962001, {0, 15392016, 46176048, 61568064, 92352096}, 95238099},
-    {P(denoise_plan(962001, 2, true, false)), 962001, {0, 15392016, 46176048, 61568064, X}, 92352096},
-    {P(denoise_plan(962001, 2, false, true)), 962001, {0, 15392016, X, 46176048, 76960080}, 79846083},
-    {P(denoise_plan(15, 0, true, true)), 15, {0, 240, 720, X, 960}, 1005},
-    {P(denoise_plan(15, 0, true, false)), 15, {0, 240, 720, X, X}, 960},
-    {P(denoise_plan(15, 0, false, true)), 15, {0, 240, X, X, 720}, 765},
-    {P(denoise_plan(15, 1, true, true)), 15, {0, 240, 720, 960, 1200}, 1245},
-    {P(denoise_plan(15, 1, true, false)), 15, {0, 240, 720, 960, X}, 1200},
-    {P(denoise_plan(15, 1, false, true)), 15, {0, 240, X, 720, 960}, 1005},
-    {P(denoise_plan(15, 2, true, true)), 15, {0, 240, 720, 960, 1440}, 1485},
-    {P(denoise_plan(15, 2, true, false)), 15, {0, 240, 720, 960, X}, 1440},
-    {P(denoise_plan(15, 2, false, true)), 15, {0, 240, X, 720, 1200}, 1245},
+    // spt_denoise(npix, planes = min(levels - 1, 2), out_rgba, out_rgb8): 1201 x 801, 5 x 3; mom and
+    // out_var, the variance-guided form's arrays, are absent and the bytes stay last
+    {P(denoise_plan(962001, 0, true, true)), 962001, {0, 15392016, 46176048, X, X, X, 61568064}, 64454067},
+    {P(denoise_plan(962001, 0, true, false)), 962001, {0, 15392016, 46176048, X, X, X, X}, 61568064},
+    {P(denoise_plan(962001, 0, false, true)), 962001, {0, 15392016, X, X, X, X, 46176048}, 49062051},
+    {P(denoise_plan(962001, 1, true, true)), 962001, {0, 15392016, 46176048, 61568064, X, X, 76960080}, 79846083},
+    {P(denoise_plan(962001, 1, true, false)), 962001, {0, 15392016, 46176048, 61568064, X, X, X}, 76960080},
+    {P(denoise_plan(962001, 1, false, true)), 962001, {0, 15392016, X, 46176048, X, X, 61568064}, 64454067},
+    {P(denoise_plan(962001, 2, true, true)), 962001, {0, 15392016, 46176048, 61568064, X, X, 92352096}, 95238099},
+    {P(denoise_plan(962001, 2, true, false)), 962001, {0, 15392016, 46176048, 61568064, X, X, X}, 92352096},
+    {P(denoise_plan(962001, 2, false, true)), 962001, {0, 15392016, X, 46176048, X, X, 76960080}, 79846083},
+    {P(denoise_plan(15, 0, true, true)), 15, {0, 240, 720, X, X, X, 960}, 1005},
+    {P(denoise_plan(15, 0, true, false)), 15, {0, 240, 720, X, X, X, X}, 960},
+    {P(denoise_plan(15, 0, false, true)), 15, {0, 240, X, X, X, X, 720}, 765},
+    {P(denoise_plan(15, 1, true, true)), 15, {0, 240, 720, 960, X, X, 1200}, 1245},
+    {P(denoise_plan(15, 1, true, false)), 15, {0, 240, 720, 960, X, X, X}, 1200},
+    {P(denoise_plan(15, 1, false, true)), 15, {0, 240, X, 720, X, X, 960}, 1005},
+    {P(denoise_plan(15, 2, true, true)), 15, {0, 240, 720, 960, X, X, 1440}, 1485},
+    {P(denoise_plan(15, 2, true, false)), 15, {0, 240, 720, 960, X, X, X}, 1440},
+    {P(denoise_plan(15, 2, false, true)), 15, {0, 240, X, 720, X, X, 1200}, 1245},
+    // spt_denoise_var(..., mom = true, out_var): 16 B of mom and 4 B of out_var per pixel (4 * 962001 =
+    // 3848004 takes 3848016, 4 * 15 = 60 takes 64) after the planes, before the bytes
+    {P(denoise_plan(962001, 2, true, true, true, true)), 962001, {0, 15392016, 46176048, 61568064, 92352096, 107744112, 111592128}, 114478131},
+    {P(denoise_plan(962001, 2, true, true, true, false)), 962001, {0, 15392016, 46176048, 61568064, 92352096, X, 107744112}, 110630115},
+    {P(denoise_plan(962001, 0, false, true, true, true)), 962001, {0, 15392016, X, X, 46176048, 61568064, 65416080}, 68302083},
+    {P(denoise_plan(962001, 1, true, false, true, false)), 962001, {0, 15392016, 46176048, 61568064, 76960080, X, X}, 92352096},
+    {P(denoise_plan(15, 2, true, true, true, true)), 15, {0, 240, 720, 960, 1440, 1680, 1744}, 1789},
+    {P(denoise_plan(15, 2, true, true, true, false)), 15, {0, 240, 720, 960, 1440, X, 1680}, 1725},
+    {P(denoise_plan(15, 0, false, true, true, true)), 15, {0, 240, X, X, 720, 960, 1024}, 1069},
+    {P(denoise_plan(15, 1, true, false, true, false)), 15, {0, 240, 720, 960, 1200, X, X}, 1440},
 };
 
 }  // namespace
