@@ -119,6 +119,17 @@ typedef struct spt_stats {
                                     accel tables, the camera or the frame size changed) */
     double accel_build_ms;       /* host time of the last traversal-table build + upload
                                     (spt_set_scene / cluster setters) */
+    /* Added at the end of the struct with SPT_ABI_VERSION still 11: a caller compiled against
+       a header without this field must be recompiled before it calls spt_get_stats, which
+       writes all of this struct (8 bytes past the older one). */
+    uint64_t fold_table_entries; /* entries of the fold's colour table, one per diffuse sample code of
+                                    the scene at the context's depth ((jmax + 1) * slots, at most 32 MiB
+                                    of 16-byte entries), built by the first launched render after the
+                                    scene or the depth changed; 0: no table (it would be larger, or
+                                    none built yet) and the fold decodes every sample word
+                                    arithmetically, as the folds of the batched host calls and of
+                                    spt_render_frame always do; member 0's on a multi-device
+                                    context */
 } spt_stats;
 
 SPT_API int spt_abi_version(void);

@@ -190,6 +190,9 @@ int launch_batch(spt_ctx *ctx, BatchSet *bs, const std::vector<BatchReq *> &batc
     }
 
     spt::FoldArgs fa = fold_args(ctx, use_svc ? ctx->svc.d_ring : w->d_samples, slot_words);
+    // the batched fold keeps the arithmetic decode (fold_kernel_batch)
+    fa.ctab = nullptr;
+    fa.ctab_n = 0;
     fa.out_rgba = any_rgba ? bs->d_stage : nullptr;
     fa.out_rgb8 = any_g ? (spec_d8 ? spec_d8 : ctx->d_frame8) : nullptr;
     fa.width = W;

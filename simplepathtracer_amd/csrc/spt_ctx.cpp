@@ -428,6 +428,38 @@ int rebuild_accel(spt_ctx *ctx)
     return SPT_OK;
 }
 
+// The fold's colour table (spt_codes.h) for the current scene tables and depth: one entry
+// per diffuse code, filled on the device by the arithmetic decode (ctab_fill_kernel).  It
+// depends on the shading table, the slot order (code_stride) and jmax only, which the scene,
+// cluster and params setters change: they leave the table stale (ctab_valid), and the first
+// launched render after them (render_impl) calls this; nothing is done while the table
+// stands.  Like the scene uploads it waits for the device on both sides: launches in flight
+// on any stream may read the old table, and the launches enqueued after it on any stream
+// read the new one.
+bool ctab_valid(const spt_ctx *ctx)
+{
+    return ctx->ctab_n != 0 && ctx->ctab_gen == ctx->accel_gen && ctx->ctab_jmax == code_jmax(ctx);
+}
+
+int rebuild_ctab(spt_ctx *ctx)
+{
+    const uint32_t jmax = code_jmax(ctx);
+    if (ctx->ctab_gen == ctx->accel_gen && ctx->ctab_jmax == jmax) return SPT_OK;
+    if (int rc = svc_end(ctx)) return rc;  // a resident session would hold the synchronisation
+    ctx->ctab_n = 0;
+    ctx->ctab_gen = ctx->accel_gen;
+    ctx->ctab_jmax = jmax;
+    if (!spt::ctab_fits(ctx->code_stride, jmax) || !spt::code_layout_fits(ctx->code_stride, jmax)) return SPT_OK;
+    const uint32_t n = (uint32_t)spt::ctab_entries(ctx->code_stride, jmax);
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    if (int rc = ensure(ctx, &ctx->d_ctab, &ctx->ctab_cap, n)) return rc;
+    spt::FoldArgs fa = fold_args(ctx, nullptr, 1u);
+    HIP_TRY(ctx, spt::launch_ctab_fill(fa, ctx->d_ctab, n, nullptr));
+    HIP_TRY(ctx, hipStreamSynchronize(nullptr));
+    ctx->ctab_n = n;
+    return SPT_OK;
+}
+
 // Wait for every render launch this context has enqueued (on any stream) -- not for the
 // device: unrelated work of the process (torch kernels, RCCL) keeps running.  The feature
 // kernels (spt_features.hip) read the candidate lists on caller streams as renders do:
@@ -694,6 +726,7 @@ int stats_one(spt_ctx *ctx, spt_stats *out)
     out->prim_list_build_ms = ctx->prim_build_s * 1e3;
     out->prim_list_builds = ctx->prim_builds;
     out->accel_build_ms = ctx->accel_build_s * 1e3;
+    out->fold_table_entries = ctab_valid(ctx) ? ctx->ctab_n : 0u;
     return SPT_OK;
 }
 
@@ -894,7 +927,7 @@ void spt_ctx_destroy(spt_ctx *ctx)
     if (ctx->ref_ev) (void)hipEventDestroy(ctx->ref_ev);
     void *bufs[] = {ctx->d_shade, ctx->d_mat, ctx->d_slots, ctx->d_orig, ctx->d_nodes,
                     ctx->d_kpre, ctx->d_counters, ctx->d_frame8, ctx->d_prim_b8, ctx->d_prim_b4,
-                    ctx->d_prim_slots};
+                    ctx->d_prim_slots, ctx->d_ctab};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     for (Workspace &w : ctx->ws) {

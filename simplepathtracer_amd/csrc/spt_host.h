@@ -302,6 +302,13 @@ struct spt_ctx {
     // diffuse sample codes (spt_internal.h diffuse_code): the slot count, and the halvings
     // after which every finite albedo of the scene is 0 (j saturates at min(bounces - 1, jz))
     uint32_t code_stride = 1, code_jz = 0;
+    // the fold's colour table (spt_codes.h): ctab_n entries for codes up to jmax = ctab_jmax,
+    // rebuilt by rebuild_ctab (the first launched render after the scene tables or jmax
+    // changed); ctab_n = 0: none (above kCtabMaxBytes), the kernels decode arithmetically
+    float4 *d_ctab = nullptr;
+    size_t ctab_cap = 0;
+    uint32_t ctab_n = 0, ctab_jmax = 0;
+    uint64_t ctab_gen = 0;  // accel_gen it was built for (0: never)
     bool scene_set = false;
     // host copy of the hit geometry, to rebuild the traversal tables
     std::vector<float> h_centers, h_radii;
@@ -448,6 +455,8 @@ int rebuild_prim(spt_ctx *ctx);
 int wait_own_renders(spt_ctx *ctx);
 int features_mark(spt_ctx *ctx, hipStream_t s);
 int rebuild_accel(spt_ctx *ctx);
+int rebuild_ctab(spt_ctx *ctx);
+bool ctab_valid(const spt_ctx *ctx);
 int ensure_wavefront(spt_ctx *ctx, Workspace *w, uint32_t cap, uint32_t qcap);
 hipStream_t companion_for(spt_ctx *ctx, hipStream_t s);
 Workspace * workspace_for(spt_ctx *ctx, hipStream_t s);
@@ -485,8 +494,8 @@ spt_ctx * pick_member(spt_ctx *ctx);
 void release_slot(spt_ctx *ctx, HostSlot *h);
 HostSlot * acquire_slot(spt_ctx *ctx, std::unique_lock<std::mutex> &lk);
 int check_region(spt_ctx *ctx, uint32_t yB, uint32_t yE, uint32_t xB, uint32_t xE);
-int render_impl(spt_ctx *ctx, int mode, const spt::RowMap &map, float4 *d_rgba, uint8_t *d_rgb8, hipStream_t s, bool keep_samples, const Progress *pg = nullptr, uint32_t grid_div = 1, const AliasRange *ar = nullptr);
-int render_task_range(spt_ctx *ctx, uint32_t i0, uint32_t i1, float4 *d_out, hipStream_t s);
+int render_impl(spt_ctx *ctx, int mode, const spt::RowMap &map, float4 *d_rgba, uint8_t *d_rgb8, hipStream_t s, bool keep_samples, const Progress *pg = nullptr, uint32_t grid_div = 1, const AliasRange *ar = nullptr, bool table = true);
+int render_task_range(spt_ctx *ctx, uint32_t i0, uint32_t i1, float4 *d_out, hipStream_t s, bool table = true);
 spt::FoldArgs fold_args(const spt_ctx *ctx, const uint32_t *samples, uint32_t slot_words);
 int spec_serve(spt_ctx *ctx, std::unique_lock<std::mutex> &lk, int mode, uint32_t yB, uint32_t yE, uint32_t xB, uint32_t xE, uint8_t *g_data);
 int spec_frame_bytes(spt_ctx *ctx, std::unique_lock<std::mutex> &lk, size_t bytes);

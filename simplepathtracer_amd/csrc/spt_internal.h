@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "spt_hip.h"
+#include "spt_codes.h"
 
 namespace spt {
 
@@ -70,31 +71,7 @@ __host__ __device__ inline void tile_pixel(uint32_t q, uint32_t width, uint32_t 
     col = c;
 }
 
-// Division of x < 2^31 by a divisor d >= 1 fixed for a launch (Granlund-Montgomery,
-// N = 31 bits): l = ceil(log2 d), m = floor(2^(31+l) / d) + 1 < 2^32, and
-// x / d == mulhi(x, m) >> (l - 1) for every x < 2^31; d == 1 passes x through.
-struct FastDiv {
-    uint32_t d, m, s;
-};
-inline FastDiv make_fastdiv(uint32_t d)
-{
-    FastDiv f{d, 0u, 0u};
-    if (d <= 1u) return f;
-    uint32_t l = 0;
-    while ((1ull << l) < d) ++l;
-    f.m = (uint32_t)(((1ull << (31 + l)) / d) + 1ull);
-    f.s = l - 1u;
-    return f;
-}
-__host__ __device__ inline uint32_t fast_div(uint32_t x, const FastDiv &f)
-{
-#ifdef __HIP_DEVICE_COMPILE__
-    const uint32_t hi = __umulhi(x, f.m);
-#else
-    const uint32_t hi = (uint32_t)(((uint64_t)x * f.m) >> 32);
-#endif
-    return f.d <= 1u ? x : hi >> f.s;
-}
+// FastDiv / fast_div (division by a launch constant): spt_codes.h
 
 // row_of with the strip division by multiply-shift (div_strip = FastDiv(m.strip))
 __host__ __device__ inline uint32_t row_of_fast(const RowMap &m, uint32_t lr, const FastDiv &div_strip)
@@ -216,55 +193,8 @@ __host__ __device__ inline void ts_slot_base(uint32_t lr, uint32_t col, uint32_t
     step = h * wt;
 }
 
-// Sample codes: one 32-bit word per sample instead of its colour.  A
-// sample's colour is one of
-//   * the sky, initColor * k * 0.5 with k = d.y + 1.f of the final ray
-//     (SampleColorSkybox, SingleThreadPathTracer.hpp:11-14): the word is k's bits;
-//   * a diffuse albedo halved 1 + j times (SampleColorDiffuse, lines 21-37: the first
-//     diffuse hit's colour * 0.5, then * 0.5 per further bounce): a code naming the
-//     first hit's slot and j;
-//   * 0 (the specular-event cap; RenderSegmentTask's dropped paths).
-// A finite k is 0 or at least 2^-24 in magnitude (fl(y + 1) for float y: only y = -1
-// lies within 2^-24 of -1), so the words whose magnitude as a float is below 2^-24 and
-// nonzero never hold a k: they carry the codes c in [1, kCodeMax], positive words
-// first, then the same magnitudes with the sign bit.  c = 1 is the colour 0,
-// c = 2 + j * stride + slot a diffuse sample (stride = the scene's slot count).  j is
-// saturated at jmax = min(bounces - 1, jz): j <= bounces - 1 always, and after jz
-// halvings every finite albedo of the scene is 0 (inf / NaN stay themselves; jz <=
-// kCodeSat, since 2^-280 * FLT_MAX rounds to 0), so saturating there changes no colour.
-// A scene fits when (jmax + 1) * stride + 1 <= kCodeMax: ~34 M slots at depth 50, ~11 M
-// for deep paths over albedos up to 255 (jz = 157).  The fold rebuilds the colour with
-// the render kernel's own operations: bit-identical.
-constexpr uint32_t kCodeSmall = 0x33800000u;        // bits of 2^-24
-constexpr uint32_t kCodeMax = 2u * (kCodeSmall - 1u);  // the largest code
-constexpr uint32_t kCodeSat = 280;                  // 2^-280 * FLT_MAX rounds to 0
-__host__ __device__ inline bool code_layout_fits(uint64_t stride, uint32_t jmax)
-{
-    return (jmax + 1ull) * stride + 1ull <= kCodeMax;
-}
-// diffuse code of (j, slot) and back (div = FastDiv(stride), defined below)
-__host__ __device__ inline uint32_t diffuse_code(uint32_t j, uint32_t slot, uint32_t stride)
-{
-    return 2u + j * stride + slot;
-}
-__host__ __device__ inline void diffuse_decode(uint32_t c, const FastDiv &div, uint32_t &j, uint32_t &slot)
-{
-    const uint32_t v = c - 2u;  // < kCodeMax < 2^31 (fast_div's range)
-    j = fast_div(v, div);
-    slot = v - j * div.d;
-}
-__host__ __device__ inline uint32_t code_word(uint32_t c)
-{
-    return c < kCodeSmall ? c : 0x80000000u | (c - kCodeSmall + 1u);
-}
-// the code of a word, 0 for a sky word
-__host__ __device__ inline uint32_t word_code(uint32_t w)
-{
-    const uint32_t a = w & 0x7FFFFFFFu;
-    if (a == 0u || a >= kCodeSmall) return 0u;
-    return (w >> 31) ? a + kCodeSmall - 1u : a;
-}
-constexpr uint32_t kZeroWord = 1u;  // code_word(1): the colour 0
+// Sample codes (code_word, word_code, diffuse_code, ...) and the colour table's indexing:
+// spt_codes.h
 
 constexpr uint32_t kMaxGroup = 16;     // sphere-table padding granule (>= SPT_GROUP)
 constexpr uint32_t kClusterSlots = 8;  // max members per cluster = slots of a tree leaf
@@ -472,6 +402,8 @@ struct FoldArgs {
     const float4 *shade;      // the scene's shading table (diffuse codes name its slots)
     float sky[3];             // initColor (sky words)
     FastDiv code_div;         // FastDiv(code stride): diffuse_decode
+    const float4 *ctab;       // the scene's colour table (spt_codes.h): entry c - 2 = the colour of diffuse
+    uint32_t ctab_n;          // code c, ctab_n >= 1 entries; null: every word is decoded arithmetically
     float4 *acc;         // persistent accumulator (w = sample count)
     float4 *out_rgba;    // nullable, local pixel order
     uint8_t *out_rgb8;   // nullable, full frame (g_data layout)
@@ -526,6 +458,9 @@ uint32_t wavefront_blocks(const AccelView &ac, int dev);
 hipError_t launch_fold(const FoldArgs &a, hipStream_t s);
 // spt_render_samples: pixels [p0, p0 + n) of the region, out[(p - p0) * spp + s]
 hipError_t launch_expand(const FoldArgs &a, float4 *out, uint32_t p0, uint32_t n, hipStream_t s);
+// ctab[i] = {decode_sample(code_word(i + 2)), +0} for i < n: the colour table of a's scene
+// (a.shade, a.code_div; spt_codes.h), filled by the arithmetic decode itself
+hipError_t launch_ctab_fill(const FoldArgs &a, float4 *ctab, uint32_t n, hipStream_t s);
 hipError_t launch_assemble(const float4 *tiles, uint32_t max_rows, RowMap base, uint32_t width, uint32_t height,
                            float4 *frame, uint8_t *rgb8, hipStream_t s);
 hipError_t launch_selftest(const float *a, const float *b, const uint32_t *bits, uint32_t n, float *out,
@@ -616,7 +551,7 @@ hipError_t launch_cast(const CastArgs &a, hipStream_t s);
 // n paths, one per lane: TraceAndSampleColor(d[i], o[i], bounces) in segment semantics,
 // every draw of path i from the raw splitmix state st[i].  The trace kernel leaves path
 // i's sample word in the first word of rgba[i] (shade_step's store); the decode pass that
-// follows it on the stream rebuilds the colour there (decode_sample), w = +0.
+// follows it on the stream rebuilds the colour there (decode_word), w = +0.
 // info (nullable) = two words per path: {casts, specular events | cut at the cap << 31}.
 struct TraceArgs {
     DeviceScene scene;  // code_jmax: the launch's own, from `bounces`

@@ -270,10 +270,20 @@ __device__ __forceinline__ uint32_t svc_find_job(uint32_t nb, uint32_t cur, uint
 
 // decode_sample for a run of words without branches around the loads: the shading-table
 // reads of all N words are issued together (slot 0 stands in for sky and zero words), the
-// colours selected afterwards; only denormal halvings (halve_n's slow path) branch.
-template <int N>
+// colours selected afterwards; only denormal halvings (halve_n's slow path) branch.  The
+// table form (TAB, spt_decode.h) issues its N table reads together likewise and has no
+// branch at all.
+template <int N, bool TAB>
 __device__ __forceinline__ void decode_run(const FoldArgs &a, const uint32_t (&w)[N], f3 (&col)[N])
 {
+    if constexpr (TAB) {
+        float4 t[N];
+#pragma unroll
+        for (int i = 0; i < N; ++i) t[i] = ctab_load(a, w[i]);
+#pragma unroll
+        for (int i = 0; i < N; ++i) col[i] = ctab_select(a, w[i], t[i]);
+        return;
+    }
     uint32_t c[N], j[N];
     float4 sh[N];
 #pragma unroll
@@ -308,6 +318,7 @@ static_assert(SPT_FOLD_RUN % kFoldDecode == 0, "fold runs are decoded kFoldDecod
 // each sample's sources are added in that order.  No source: 0 samples, and 0 * (1.f / 0)
 // is NaN, as in the reference.  The sources' slots are those of rows [row0, row0 + rows)
 // of the launch (the call's own rows, or a range of them: spt_render_frame).
+template <bool TAB>
 __device__ __forceinline__ void alias_accumulate(const FoldArgs &a, const uint32_t *samples, uint32_t p, uint32_t W,
                                                  uint32_t H, uint32_t row0, uint32_t rows, uint32_t S, float4 &acc)
 {
@@ -316,7 +327,7 @@ __device__ __forceinline__ void alias_accumulate(const FoldArgs &a, const uint32
     const uint32_t ns = dy_hi + 1u - dy_lo;  // sources: pixels (p - dy H, dy)
     const uint2 *s2 = (const uint2 *)samples;
     auto add = [&](uint32_t w) {
-        const f3 c = decode_sample(a, w);
+        const f3 c = decode_word<TAB>(a, w);
         acc.x = acc.x + c.x;
         acc.y = acc.y + c.y;
         acc.z = acc.z + c.z;
@@ -385,6 +396,7 @@ __device__ __forceinline__ void alias_accumulate(const FoldArgs &a, const uint32
 // (map, `rows` rows, alias: task mode on a non-square tile) whose slots start at
 // `samples` (item order of a batch of a.spp_batch samples: ts_slot_base); local float4
 // output at out_rgba[lr * width + col].
+template <bool TAB>
 __device__ __forceinline__ void fold_pixel(const FoldArgs &a, const uint32_t *samples, const RowMap &map,
                                            uint32_t rows, int alias, uint32_t lr, uint32_t col, float4 *out_rgba,
                                            uint8_t *out_rgb8)
@@ -397,31 +409,54 @@ __device__ __forceinline__ void fold_pixel(const FoldArgs &a, const uint32_t *sa
     if (a.mode == 0) {
         // RenderSegment: one word per slot, every sample counts.  Runs of kFoldRun words
         // are loaded before any is decoded (the loads of a run are in flight together),
-        // then decoded kFoldDecode (8) at a time
+        // then decoded kFoldDecode (8) at a time.  The table form reads the words through a
+        // pointer stepped from sample to sample (one 64-bit add per word) and adds a run's
+        // sample count at once; the arithmetic form is the code of before (ps and stp are
+        // dead there).  acc.w is read in one place, the task modes' scale 1 / acc.w below:
+        // this mode scales by 1 / s_done and only carries acc.w through a.acc between sample
+        // batches, so the two forms' counts, which part ways at 2^24 samples (+1.f sticks
+        // there, +8.f does not), reach no output
         constexpr int kFoldRun = SPT_FOLD_RUN;
+        const uint32_t *ps = samples + q0;
+        const size_t stp = step;
         uint32_t k = 0;
         for (; k + kFoldRun <= S; k += kFoldRun) {
             uint32_t w[kFoldRun];
 #pragma unroll
-            for (int i = 0; i < kFoldRun; ++i) w[i] = samples[q0 + (k + i) * step];
+            for (int i = 0; i < kFoldRun; ++i) {
+                if constexpr (TAB) {
+                    w[i] = *ps;
+                    ps += stp;
+                } else {
+                    w[i] = samples[q0 + (k + i) * step];
+                }
+            }
 #pragma unroll
             for (int g = 0; g < kFoldRun; g += kFoldDecode) {
                 uint32_t w8[kFoldDecode];
 #pragma unroll
                 for (int i = 0; i < kFoldDecode; ++i) w8[i] = w[g + i];
                 f3 c[kFoldDecode];
-                decode_run<kFoldDecode>(a, w8, c);
+                decode_run<kFoldDecode, TAB>(a, w8, c);
 #pragma unroll
                 for (int i = 0; i < kFoldDecode; ++i) {
                     acc.x = acc.x + c[i].x;
                     acc.y = acc.y + c[i].y;
                     acc.z = acc.z + c[i].z;
-                    acc.w = acc.w + 1.f;
+                    if constexpr (!TAB) acc.w = acc.w + 1.f;
                 }
             }
+            if constexpr (TAB) acc.w = acc.w + (float)kFoldRun;
         }
         for (; k < S; ++k) {
-            const f3 c = decode_sample(a, samples[q0 + k * step]);
+            uint32_t w;
+            if constexpr (TAB) {
+                w = *ps;
+                ps += stp;
+            } else {
+                w = samples[q0 + k * step];
+            }
+            const f3 c = decode_word<TAB>(a, w);
             acc.x = acc.x + c.x;
             acc.y = acc.y + c.y;
             acc.z = acc.z + c.z;
@@ -433,7 +468,7 @@ __device__ __forceinline__ void fold_pixel(const FoldArgs &a, const uint32_t *sa
         for (uint32_t k = 0; k < S; ++k) {
             const uint2 v = s2[q0 + k * step];
             if (v.y != 0u) {
-                const f3 c = decode_sample(a, v.x);
+                const f3 c = decode_word<TAB>(a, v.x);
                 acc.x = acc.x + c.x;
                 acc.y = acc.y + c.y;
                 acc.z = acc.z + c.z;
@@ -441,7 +476,7 @@ __device__ __forceinline__ void fold_pixel(const FoldArgs &a, const uint32_t *sa
             }
         }
     } else {
-        alias_accumulate(a, samples, p, W, rows, 0u, rows, S, acc);
+        alias_accumulate<TAB>(a, samples, p, W, rows, 0u, rows, S, acc);
     }
     if (!a.last) {
         a.acc[p] = acc;
@@ -1088,6 +1123,8 @@ __global__ __launch_bounds__(kLdsBlock)
 #ifndef SPT_FOLD_BLOCK
 #define SPT_FOLD_BLOCK 256
 #endif
+// (TAB: the colour-table decode or the arithmetic one, spt_decode.h; launch_fold picks)
+template <bool TAB>
 __global__ __launch_bounds__(SPT_FOLD_BLOCK) void fold_kernel(FoldArgs a)
 {
     // a launched render's fold runs beside the next frame's persistent render launch, whose
@@ -1102,18 +1139,19 @@ __global__ __launch_bounds__(SPT_FOLD_BLOCK) void fold_kernel(FoldArgs a)
     const uint32_t rows = a.npix / a.map.width;
     uint32_t lr, col;
     tile_pixel(i, a.map.width, rows, lr, col);
-    fold_pixel(a, a.samples, a.map, rows, a.alias, lr, col, a.out_rgba, a.out_rgb8);
+    fold_pixel<TAB>(a, a.samples, a.map, rows, a.alias, lr, col, a.out_rgba, a.out_rgb8);
 }
 
 // Range alias fold (FoldArgs::range_alias): output t is alias index out_i0 + t, local
 // float4 output at out_rgba[t] (g_data is written by the assemble step).
+template <bool TAB>
 __global__ __launch_bounds__(256) void fold_alias_range_kernel(FoldArgs a)
 {
     if (a.prio) __builtin_amdgcn_s_setprio(3);  // as fold_kernel
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= a.npix) return;
     float4 acc = a.first ? make_float4(0.f, 0.f, 0.f, 0.f) : a.acc[t];
-    alias_accumulate(a, a.samples, a.out_i0 + t, a.map.width, a.alias_h, a.map.y0, a.src_rows, a.spp_batch, acc);
+    alias_accumulate<TAB>(a, a.samples, a.out_i0 + t, a.map.width, a.alias_h, a.map.y0, a.src_rows, a.spp_batch, acc);
     if (!a.last) {
         a.acc[t] = acc;
         if (!a.preview) return;
@@ -1135,7 +1173,8 @@ __device__ __forceinline__ uint32_t fold_rect(crect_k *rs, uint32_t n, uint32_t 
 }
 
 // Batched fold (FoldArgs::rects): pixel i of the batch's concatenated rectangles.  Block
-// 0 also zeroes the render's claim counters for the workspace's next batch.
+// 0 also zeroes the render's claim counters for the workspace's next batch.  The batched
+// fold keeps the arithmetic decode (launch_batch passes no colour table).
 __global__ __launch_bounds__(256) void fold_kernel_batch(FoldArgs a)
 {
 #ifndef SPT_FOLD_PRIO_BATCH
@@ -1154,7 +1193,7 @@ __global__ __launch_bounds__(256) void fold_kernel_batch(FoldArgs a)
     const RowMap map{r.y0, r.y0 + r.rows, 1u, 1u, 0u, r.x0, r.w};
     uint32_t lr, col;
     tile_pixel(i - r.pix_off, r.w, r.rows, lr, col);
-    fold_pixel(a, a.samples + (size_t)a.slot_words * r.slot_off, map, r.rows, (int)r.alias, lr, col,
+    fold_pixel<false>(a, a.samples + (size_t)a.slot_words * r.slot_off, map, r.rows, (int)r.alias, lr, col,
                a.out_rgba ? a.out_rgba + r.pix_off : nullptr, r.rgb8);
 }
 
@@ -1175,6 +1214,16 @@ __global__ __launch_bounds__(256) void expand_kernel(FoldArgs a, float4 *out, ui
         const f3 c = decode_sample(a, w);
         out[(size_t)i * a.spp_batch + k] = make_float4(c.x, c.y, c.z, counted ? 1.f : 0.f);
     }
+}
+
+// The colour table of a's scene (spt_codes.h): entry i = decode_sample's colour of diffuse
+// code i + 2, w = +0.
+__global__ __launch_bounds__(256) void ctab_fill_kernel(FoldArgs a, float4 *ctab, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const f3 c = decode_sample(a, code_word(i + 2u));
+    ctab[i] = make_float4(c.x, c.y, c.z, 0.f);
 }
 
 __global__ __launch_bounds__(256) void assemble_kernel(const float4 *tiles, uint32_t max_rows, RowMap base,
@@ -1330,12 +1379,15 @@ hipError_t launch_render_svc(const RenderArgs &a, uint32_t grid, hipStream_t s)
 hipError_t launch_fold(const FoldArgs &a, hipStream_t s)
 {
     if (a.npix == 0) return hipSuccess;
+    const bool tab = fold_uses_table(a);
     if (a.range_alias)
-        hipLaunchKernelGGL(fold_alias_range_kernel, dim3((a.npix + 255) / 256), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(tab ? fold_alias_range_kernel<true> : fold_alias_range_kernel<false>, dim3((a.npix + 255) / 256),
+                           dim3(256), 0, s, a);
     else if (a.rects)
         hipLaunchKernelGGL(fold_kernel_batch, dim3((a.npix + 255) / 256), dim3(256), 0, s, a);
     else
-        hipLaunchKernelGGL(fold_kernel, dim3((a.npix + SPT_FOLD_BLOCK - 1) / SPT_FOLD_BLOCK), dim3(SPT_FOLD_BLOCK), 0, s, a);
+        hipLaunchKernelGGL(tab ? fold_kernel<true> : fold_kernel<false>, dim3((a.npix + SPT_FOLD_BLOCK - 1) / SPT_FOLD_BLOCK),
+                           dim3(SPT_FOLD_BLOCK), 0, s, a);
     return hipGetLastError();
 }
 
@@ -1343,6 +1395,13 @@ hipError_t launch_expand(const FoldArgs &a, float4 *out, uint32_t p0, uint32_t n
 {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(expand_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a, out, p0, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_ctab_fill(const FoldArgs &a, float4 *ctab, uint32_t n, hipStream_t s)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(ctab_fill_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a, ctab, n);
     return hipGetLastError();
 }
 

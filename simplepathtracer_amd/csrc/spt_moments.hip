@@ -5,7 +5,8 @@
 // One lane per pixel, in the fold's order: thread i takes the i-th pixel of the region's
 // 8x8 tiles (tile_pixel), so the 64 lanes of a wave read 64 consecutive words per sample
 // (ts_slot_base) -- one 256-byte run, as fold_kernel.  A lane keeps kMomRun words' loads in
-// flight before it decodes any (decode_sample, the fold's own colour of a word), then adds
+// flight before it decodes any (decode_word, the fold's own colour of a word: through the
+// scene's colour table where the context has one, TAB), then adds
 // them in sample order; the remainder goes word by word.  One float4 store per pixel, in
 // local row-major order (so a wave's stores are eight 128-byte rows of a tile).  The pass is
 // bound by memory: 4 B read per sample, 16 B written per pixel.
@@ -19,6 +20,7 @@ namespace spt {
 #endif
 constexpr int kMomRun = SPT_MOM_RUN;
 
+template <bool TAB>
 __global__ __launch_bounds__(256) void moments_kernel(FoldArgs a, float4 *mom)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -29,7 +31,7 @@ __global__ __launch_bounds__(256) void moments_kernel(FoldArgs a, float4 *mom)
     ts_slot_base(lr, col, W, rows, S, q0, step);
     float s1 = 0.0f, s2 = 0.0f;
     auto add = [&](uint32_t w) {
-        const f3 c = decode_sample(a, w);
+        const f3 c = decode_word<TAB>(a, w);
         const float L = (c.x * 0.2126f + c.y * 0.7152f) + c.z * 0.0722f;
         s1 = s1 + L;
         s2 = s2 + L * L;
@@ -52,7 +54,7 @@ __global__ __launch_bounds__(256) void moments_kernel(FoldArgs a, float4 *mom)
 hipError_t launch_moments(const FoldArgs &f, float4 *mom, hipStream_t s)
 {
     if (f.npix == 0) return hipSuccess;
-    hipLaunchKernelGGL(moments_kernel, dim3((f.npix + 255u) / 256u), dim3(256), 0, s, f, mom);
+    hipLaunchKernelGGL(fold_uses_table(f) ? moments_kernel<true> : moments_kernel<false>, dim3((f.npix + 255u) / 256u), dim3(256), 0, s, f, mom);
     return hipGetLastError();
 }
 

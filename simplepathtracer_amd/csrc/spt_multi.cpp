@@ -9,14 +9,14 @@
 // the range folded.  Called with ctx->mu held.
 namespace spt_api {
 
-int render_task_range(spt_ctx *ctx, uint32_t i0, uint32_t i1, float4 *d_out, hipStream_t s)
+int render_task_range(spt_ctx *ctx, uint32_t i0, uint32_t i1, float4 *d_out, hipStream_t s, bool table)
 {
     const uint32_t W = ctx->W, H = ctx->H;
     if (i1 <= i0) return SPT_OK;
     const uint32_t dy_lo = i0 >= W ? (i0 - W + H) / H : 0u, dy_hi = std::min(H - 1u, (i1 - 1u) / H);
     const spt::RowMap map{std::min(dy_lo, H), std::max(std::min(dy_lo, H), dy_hi + 1u), 1u, 1u, 0u, 0u, W};
     const AliasRange ar{i0, i1 - i0, H};
-    return render_impl(ctx, SPT_MODE_TASK, map, d_out, nullptr, s, false, nullptr, 1, &ar);
+    return render_impl(ctx, SPT_MODE_TASK, map, d_out, nullptr, s, false, nullptr, 1, &ar, table);
 }
 
 }  // namespace spt_api
@@ -184,11 +184,13 @@ int spt_render_frame(spt_ctx *ctx, int mode, float *rgba_out, uint8_t *g_data)
         float4 *dst = r == 0 ? ctx->d_tile : c->d_tile;
         if (alias) {
             const auto [i0, i1] = range_of(r);
-            if ((rc = render_task_range(c, i0, i1, dst, c->stream)))
+            // (spt_render_frame's members neither build nor read the fold's colour table:
+            // DESIGN.md §7 "The batched fold")
+            if ((rc = render_task_range(c, i0, i1, dst, c->stream, false)))
                 return r == 0 ? rc : fail(ctx, rc, "member device %d: %s", c->device, c->err.c_str());
         } else {
             spt::RowMap map{0, H, strip, parts, r, 0, W};
-            if ((rc = render_impl(c, mode, map, dst, nullptr, c->stream, false)))
+            if ((rc = render_impl(c, mode, map, dst, nullptr, c->stream, false, nullptr, 1, nullptr, false)))
                 return r == 0 ? rc : fail(ctx, rc, "member device %d: %s", c->device, c->err.c_str());
         }
         if (r > 0) HIP_TRY(ctx, hipEventRecord(c->frame_ev, c->stream));

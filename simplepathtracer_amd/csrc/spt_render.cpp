@@ -5,7 +5,8 @@
 namespace spt_api {
 
 // Fold arguments shared by every fold of ctx: the slots and the decode tables of the
-// sample words (shading table, sky colour, code stride).
+// sample words (shading table, sky colour, code stride, and the colour table where the
+// context has one: rebuild_ctab).
 spt::FoldArgs fold_args(const spt_ctx *ctx, const uint32_t *samples, uint32_t slot_words)
 {
     spt::FoldArgs fa{};
@@ -14,19 +15,31 @@ spt::FoldArgs fold_args(const spt_ctx *ctx, const uint32_t *samples, uint32_t sl
     fa.shade = ctx->d_shade;
     for (int j = 0; j < 3; ++j) fa.sky[j] = ctx->cam.sky[j];
     fa.code_div = spt::make_fastdiv(ctx->code_stride);
+    // (a table the setters left stale is not used: rebuild_ctab, render_impl)
+    fa.ctab = ctab_valid(ctx) ? ctx->d_ctab : nullptr;
+    fa.ctab_n = fa.ctab ? ctx->ctab_n : 0u;
     return fa;
 }
 
 // grid_div: concurrent host calls on this context share the GPU (render_grid)
+// table: the launch's fold may go through the colour table, built here when the setters left
+// it stale (false: spt_render_frame's members, which keep the arithmetic decode)
 int render_impl(spt_ctx *ctx, int mode, const spt::RowMap &map, float4 *d_rgba, uint8_t *d_rgb8, hipStream_t s,
-                bool keep_samples, const Progress *pg, uint32_t grid_div, const AliasRange *ar)
+                bool keep_samples, const Progress *pg, uint32_t grid_div, const AliasRange *ar, bool table)
 {
+    auto no_table = [&](spt::FoldArgs &f) {
+        if (!table) {
+            f.ctab = nullptr;
+            f.ctab_n = 0;
+        }
+    };
     const uint32_t rows = spt::rows_owned(map);
     const uint64_t npix64 = (uint64_t)rows * map.width;
     if (npix64 == 0 && ar && ar->n) {
         // a colorIndex range no pixel maps into: its outputs are 0 * (1.f / 0) = NaN
         // (TaskBasedPathTracer.hpp:196-205); the fold writes them without sources
         spt::FoldArgs fa = fold_args(ctx, nullptr, 2u);
+        no_table(fa);
         fa.out_rgba = d_rgba;
         fa.map = map;
         fa.width = ctx->W;
@@ -46,6 +59,9 @@ int render_impl(spt_ctx *ctx, int mode, const spt::RowMap &map, float4 *d_rgba, 
     if (npix64 > 0x7FFFFFFFull) return fail(ctx, SPT_ERR_ARG, "region too large (%llu pixels)", (unsigned long long)npix64);
     const uint32_t npix = (uint32_t)npix64;
     const uint32_t slot_words = mode == SPT_MODE_SEGMENT ? 1u : 2u;  // task mode keeps the path's order key
+    // the fold's colour table for the current scene tables and depth (built once per change)
+    if (table)
+        if (int rc_ = rebuild_ctab(ctx)) return rc_;
     uint64_t budget = std::max<uint64_t>(ctx->ws_bytes / (slot_words * sizeof(uint32_t)), 1);
     budget = std::min<uint64_t>(budget, 0x7FFFFFFFull);
     uint64_t per = std::max<uint64_t>(1, budget / npix);
@@ -115,6 +131,7 @@ int render_impl(spt_ctx *ctx, int mode, const spt::RowMap &map, float4 *d_rgba, 
     ra.counters = ctx->d_counters;
 
     spt::FoldArgs fa = fold_args(ctx, w->d_samples, slot_words);
+    no_table(fa);
     fa.acc = w->d_acc;
     fa.out_rgba = d_rgba;
     fa.out_rgb8 = d_rgb8;

@@ -43,7 +43,14 @@ spt::TraceArgs trace_args(const spt_ctx *ctx, uint32_t bounces)
 int trace_launch(spt_ctx *ctx, const spt::TraceArgs &a, hipStream_t s)
 {
     if (int rc = svc_end(ctx)) return rc;
-    HIP_TRY(ctx, spt::launch_trace(a, fold_args(ctx, nullptr, 1), s));
+    spt::FoldArgs f = fold_args(ctx, nullptr, 1);
+    // the colour table holds the codes of the context's depth; a call deeper than that
+    // writes codes past it and decodes them arithmetically
+    if (f.ctab && a.scene.code_jmax > ctx->ctab_jmax) {
+        f.ctab = nullptr;
+        f.ctab_n = 0;
+    }
+    HIP_TRY(ctx, spt::launch_trace(a, f, s));
     return SPT_OK;
 }
 

@@ -21,7 +21,7 @@
 // shade_step stores a finished path's sample word at samples[item]; with samples = the
 // rgba output and item = 4 i the word lands in the first word of rgba[i].  A second, small
 // kernel on the same stream turns each word into its colour in place with the fold's own
-// decode_sample (spt_decode.h).  (Decoding in the trace kernel would need the word back
+// decode_word (spt_decode.h).  (Decoding in the trace kernel would need the word back
 // from memory: a store-to-load round trip in every iteration in which a path ends.)
 #include "spt_query.h"
 #include "spt_decode.h"
@@ -175,11 +175,13 @@ __global__ __launch_bounds__(kTraceLdsBlock) __attribute__((amdgpu_waves_per_eu(
 }
 
 // each path's sample word, in the first word of its rgba slot, to its colour (w = +0)
+// (TAB: through the scene's colour table, spt_decode.h)
+template <bool TAB>
 __global__ __launch_bounds__(256) void trace_decode_kernel(FoldArgs f, float4 *rgba, uint32_t n)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
-    const f3 c = decode_sample(f, f.samples[4u * i]);
+    const f3 c = decode_word<TAB>(f, f.samples[4u * i]);
     rgba[i] = make_float4(c.x, c.y, c.z, 0.f);
 }
 
@@ -201,7 +203,7 @@ hipError_t launch_trace(const TraceArgs &all, const FoldArgs &fa, hipStream_t s)
         if (e != hipSuccess) return e;
         FoldArgs f = fa;
         f.samples = (const uint32_t *)a.rgba;
-        hipLaunchKernelGGL(trace_decode_kernel, dim3((a.n + 255u) / 256u), dim3(256), 0, s, f, a.rgba, a.n);
+        hipLaunchKernelGGL(fold_uses_table(f) ? trace_decode_kernel<true> : trace_decode_kernel<false>, dim3((a.n + 255u) / 256u), dim3(256), 0, s, f, a.rgba, a.n);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     return hipSuccess;
