@@ -596,6 +596,71 @@ SPT_API int spt_denoise_var(spt_ctx *ctx, uint32_t width, uint32_t height, const
                             float sigma_depth, float var_floor, uint32_t levels, float *out_rgba /*nullable*/,
                             uint8_t *out_rgb8 /*nullable*/, float *out_var /*nullable*/);
 
+/* ---- adaptive sampling: stop converged 8x8 tiles, keep sampling the rest
+ * A render whose sample count varies over the image.  The keyed stream per (pixel, sample)
+ * makes it well defined: a pixel that stops after n samples equals that pixel of a plain
+ * render at spp = n, bit for bit, as spt_render_progressive's passes do.
+ * Parameters.  base_spp >= 1, step_spp >= 1, max_spp >= base_spp; tol >= 0, or +inf;
+ * lum_floor finite and >= 0.
+ * Scope.  SPT_MODE_SEGMENT only; one rectangle [yBegin, yEnd) x [xBegin, xEnd) of the frame
+ * of spt_set_params, with no row map.  The context's own spp is not read; its width, height,
+ * bounces and seed are.
+ * Tiles.  The tiles are the region's 8x8 tiles anchored at (xBegin, yBegin), row-major,
+ * ragged at the right and bottom edges.  All pixels of a tile always have the same sample
+ * count n.
+ * State per pixel.  acc (3 floats), s1, s2, all starting at +0.  c_s is the colour of sample
+ * s as the fold decodes it, L_s as in "sample moments".  Sample s of a pixel is added as
+ *   acc.c = acc.c + c_s.c;  s1 = s1 + L_s;  s2 = s2 + L_s * L_s
+ * in sample order; fp32, one rounding per operation written, no contraction.
+ * Passes.  Pass 0 gives every tile samples [0, base_spp).  After a pass in which the active
+ * tiles reached n samples, for each pixel of an active tile:
+ *   inv = 1.0f / (float)n;  m1 = s1 * inv;  m2 = s2 * inv
+ *   d = m2 - m1 * m1;  var = d < 0 ? +0 : d           (NaN stays NaN)
+ *   e = var * inv                                      (variance of the pixel mean)
+ *   r = (m1 + lum_floor) * tol;  thr = r * r
+ *   unconverged = e > thr                              (NaN compares false: such a pixel counts as converged)
+ * A tile stays active iff n < max_spp and any of its pixels is unconverged.  The next pass
+ * gives every active tile samples [n, n + min(step_spp, max_spp - n)); n is therefore
+ * launch-uniform over the active tiles.  A tile that has gone inactive never returns.  The
+ * loop ends when no tile is active.  With tol = +inf every tile stops at base_spp; with
+ * tol = 0 exactly the tiles with some var > 0 run to max_spp.
+ * Outputs.  Each pixel's outputs are written when its tile goes inactive, with that n:
+ *   rgba_out  {acc.r * inv, acc.g * inv, acc.b * inv, +0}: what spt_render_segment writes at
+ *             spp = n, on bits
+ *   g_data    io::WritePixel's bytes of that colour, in the reference layout; other bytes are
+ *             left untouched
+ *   mom       {m1, m2, var, (float)n}, float4 in local pixel order: the layout
+ *             spt_denoise_var reads; mom.w is the spp map
+ *   info      (nullable, 2 x uint64) total samples rendered, and passes run
+ * Limits and errors.  A pass's sample words must fit one sample batch of the workspace: at
+ * most 2^31 - 1 items, within spt_set_workspace; the calls check the largest pass their
+ * parameters allow (every tile, the longest pass) before anything is launched: SPT_ERR_ARG
+ * otherwise, and nothing is rendered.  SPT_ERR_STATE without scene, camera or params.
+ * SPT_ERR_ARG, with every output untouched, for a null mom together with null rgba_out and
+ * g_data, a bad rectangle, and parameters outside the ranges above, NaN included.  An empty
+ * rectangle is SPT_OK and touches nothing.
+ * Behaviour.  The calls use member 0 of a multi-device context, end a resident service
+ * session first (as the moments do) and ignore the engine setting: the passes are batched
+ * launches of the megakernel.  spt_stats counts them as the renders they are: samples, casts,
+ * one launch per pass.
+ * Known limit.  A tile whose first base_spp samples all agree stops there, even if a later
+ * sample would have differed (a small bright feature every early sample missed): base_spp is
+ * the guard.  Activity does not spread to neighbouring tiles. */
+/* host pointers, blocking */
+SPT_API int spt_render_adaptive(spt_ctx *ctx, uint32_t yBegin, uint32_t yEnd, uint32_t xBegin, uint32_t xEnd,
+                                uint32_t base_spp, uint32_t step_spp, uint32_t max_spp, float tol, float lum_floor,
+                                float *rgba_out /*nullable*/, uint8_t *g_data /*nullable*/, float *mom /*nullable*/,
+                                uint64_t *info /*nullable*/);
+/* device pointers (d_rgb8: the full frame, g_data layout; info: host memory), on `stream`
+ * (NULL = default stream).  Not fully asynchronous, hence the name: which tiles a pass
+ * renders decides its launch's grid and item count, so the host waits on `stream` once per
+ * pass for the plan's counts -- and with it for whatever was queued on `stream` before the
+ * call.  It returns with the last pass's fold enqueued and info written. */
+SPT_API int spt_render_adaptive_dev(spt_ctx *ctx, uint32_t yBegin, uint32_t yEnd, uint32_t xBegin, uint32_t xEnd,
+                                    uint32_t base_spp, uint32_t step_spp, uint32_t max_spp, float tol, float lum_floor,
+                                    void *d_rgba /*nullable*/, void *d_rgb8 /*nullable*/, void *d_mom /*nullable*/,
+                                    uint64_t *info /*nullable*/, void *stream);
+
 SPT_API int spt_get_stats(spt_ctx *ctx, spt_stats *out);
 SPT_API int spt_reset_stats(spt_ctx *ctx);
 

@@ -925,9 +925,11 @@ void spt_ctx_destroy(spt_ctx *ctx)
     for (const spt_ctx::Pinned &p : ctx->pinned)
         if (p.owner) (void)hipHostUnregister(p.ptr);
     if (ctx->ref_ev) (void)hipEventDestroy(ctx->ref_ev);
+    if (ctx->ad_done) (void)hipEventDestroy(ctx->ad_done);
+    if (ctx->ad_count) (void)hipHostFree(ctx->ad_count);
     void *bufs[] = {ctx->d_shade, ctx->d_mat, ctx->d_slots, ctx->d_orig, ctx->d_nodes,
                     ctx->d_kpre, ctx->d_counters, ctx->d_frame8, ctx->d_prim_b8, ctx->d_prim_b4,
-                    ctx->d_prim_slots, ctx->d_ctab};
+                    ctx->d_prim_slots, ctx->d_ctab, ctx->ad_acc, ctx->ad_s12, ctx->ad_flags, ctx->ad_rects};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     for (Workspace &w : ctx->ws) {

@@ -12,6 +12,8 @@
 //   spt_features.cpp feature buffers (spt_render_features[_async])
 //   spt_denoise.cpp  the denoiser (spt_denoise[_async], spt_denoise_var[_async])
 //   spt_moments.cpp  per-pixel sample moments (spt_render_moments[_async])
+//   spt_adaptive.cpp adaptive sampling (spt_render_adaptive[_dev]); spt_adaptive.h is the tile plan
+//                    it shares with spt_adaptive.hip and the host check
 //   spt_staging.cpp  the device staging of their blocking forms; spt_staging.h is its
 //                    HIP-free half (the plan: chunk size, offsets, total)
 // The context owns the device copy of the reference's global state (scene SoA, camera,
@@ -22,6 +24,7 @@
 #pragma once
 #include "spt_hip.h"
 #include "spt_accel.h"
+#include "spt_adaptive.h"
 #include "spt_internal.h"
 #include "spt_readahead.h"
 #include "spt_staging.h"
@@ -351,6 +354,17 @@ struct spt_ctx {
     unsigned long long *d_counters = nullptr;
     uint8_t *d_frame8 = nullptr;
     size_t frame8_cap = 0;
+    // adaptive sampling (spt_adaptive.cpp): per region pixel the in-order sums {acc.rgb, -} and
+    // {s1, s2}, per 8x8 tile its flag and its rectangle of the current pass, grown on demand and
+    // reused across calls; the plan's counts in page-locked host words; the event behind a
+    // call's last fold, which the next call's stream waits for before it touches the state
+    float4 *ad_acc = nullptr;
+    float2 *ad_s12 = nullptr;
+    uint32_t *ad_flags = nullptr;
+    spt::BatchRect *ad_rects = nullptr;
+    size_t ad_acc_cap = 0, ad_s12_cap = 0, ad_flags_cap = 0, ad_rects_cap = 0;
+    spt::AdaptCount *ad_count = nullptr;
+    hipEvent_t ad_done = nullptr;
 
     // host buffers registered by spt_pin_host, with their device-side addresses
     struct Pinned {

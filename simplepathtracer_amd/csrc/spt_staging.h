@@ -1,5 +1,6 @@
 // spt_staging.h -- device staging of the blocking queries (spt_cast_rays, spt_primary_hits,
-// spt_trace_rays, spt_render_features, spt_denoise, spt_denoise_var, spt_render_moments): one
+// spt_trace_rays, spt_render_features, spt_denoise, spt_denoise_var, spt_render_moments,
+// spt_render_adaptive): one
 // device allocation cut into the arrays of a chunk of the call's items (rays, rows of
 // pixels, or the whole image), which the call copies in, launches over and copies out chunk
 // by chunk.  One plan per form (the two filters share denoise_plan: the variance-guided one
@@ -91,6 +92,12 @@ inline StagingPlan denoise_plan(size_t npix, size_t planes, bool out, bool rgb8,
 inline StagingPlan moments_plan(size_t npix, size_t frame_bytes, bool rgba, bool g_data)
 {
     const StagingArray a[3] = {{npix * 16, rgba}, {npix * 16}, {frame_bytes, g_data, true}};
+    return staging_plan(a, 3, 1, StagingItems::kAll);
+}
+// spt_render_adaptive, the whole region as one item: moments_plan with mom optional too
+inline StagingPlan adaptive_staging_plan(size_t npix, size_t frame_bytes, bool rgba, bool mom, bool g_data)
+{
+    const StagingArray a[3] = {{npix * 16, rgba}, {npix * 16, mom}, {frame_bytes, g_data, true}};
     return staging_plan(a, 3, 1, StagingItems::kAll);
 }
 

@@ -455,15 +455,66 @@ class Context:
             ctypes.c_void_p(d_out or None), ctypes.c_void_p(d_rgb8 or None), ctypes.c_void_p(d_out_var or None),
             ctypes.c_void_p(d_scratch or None), ctypes.c_void_p(stream or None)))
 
-    def render_denoised(self, variance=False, **sigmas) -> np.ndarray:
+    def render_adaptive(self, yB, yE, xB, xE, base_spp=8, step_spp=8, max_spp=64, tol=0.08, lum_floor=1.0, g_data=None):
+        """An adaptively sampled segment-mode render of the rectangle (spt_render_adaptive):
+        every 8x8 tile of it gets base_spp samples, then step_spp more per pass while any of
+        its pixels' mean is still noisier than tol (relative to its luminance + lum_floor), up
+        to max_spp.  Returns (rgba, mom, info): rgba of shape (pixels, 4), each pixel what
+        render_segment gives at its own sample count; mom of shape (pixels, 4) as
+        render_moments', mom[:, 3] the per-pixel sample count; info a dict with the samples
+        rendered and the passes run.  Writes g_data bytes of the region if given.  The
+        context's own spp is not read."""
+        n = max(yE - yB, 0) * max(xE - xB, 0)
+        out = np.zeros((n, 4), np.float32)
+        mom = np.zeros((n, 4), np.float32)
+        info = np.zeros(2, np.uint64)
+        gp = None
+        if g_data is not None:
+            assert g_data.dtype == np.uint8 and g_data.flags.c_contiguous
+            gp = _p(g_data)
+        self._check(_native.lib().spt_render_adaptive(self._h, yB, yE, xB, xE, int(base_spp), int(step_spp), int(max_spp),
+                                                      tol, lum_floor, _p(out), gp, _p(mom), _p(info)))
+        return out, mom, {"samples": int(info[0]), "passes": int(info[1])}
+
+    def render_adaptive_dev(self, yB, yE, xB, xE, base_spp=8, step_spp=8, max_spp=64, tol=0.08, lum_floor=1.0, rgba=None,
+                            rgb8=None, mom=None, stream=0) -> dict:
+        """render_adaptive into torch tensors on the context's device (spt_render_adaptive_dev):
+        rgba and mom float32 with 4 floats per region pixel, rgb8 the full frame's g_data
+        bytes (uint8), each optional; on `stream` (a hipStream_t; 0 = the default stream).
+        The host waits on the stream once per pass, and the call returns with the last pass's
+        fold enqueued: synchronise the stream before reading the tensors.  Returns info."""
+        n = max(yE - yB, 0) * max(xE - xB, 0)
+        for t, what, count in ((rgba, "rgba", n * 4), (mom, "mom", n * 4)):
+            if t is not None and not (t.is_cuda and t.is_contiguous() and t.dtype.is_floating_point and
+                                      t.element_size() == 4 and t.numel() == count):
+                raise ValueError(f"{what}: expected a contiguous float32 device tensor of {count} elements")
+        if rgb8 is not None and not (rgb8.is_cuda and rgb8.is_contiguous() and rgb8.element_size() == 1 and
+                                     self._frame is not None and rgb8.numel() == self._frame[0] * self._frame[1] * 3):
+            raise ValueError("rgb8: expected a contiguous uint8 device tensor of the frame's W * H * 3 bytes")
+        info = np.zeros(2, np.uint64)
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)  # noqa: E731
+        self._check(_native.lib().spt_render_adaptive_dev(self._h, yB, yE, xB, xE, int(base_spp), int(step_spp),
+                                                          int(max_spp), tol, lum_floor, ptr(rgba), ptr(rgb8), ptr(mom),
+                                                          _p(info), ctypes.c_void_p(stream or None)))
+        return {"samples": int(info[0]), "passes": int(info[1])}
+
+    def render_denoised(self, variance=False, adaptive=None, **sigmas) -> np.ndarray:
         """The current frame rendered, its feature buffers, and the frame filtered by denoise
         (whose keyword arguments `sigmas` takes): render_frame + feature_buffers + denoise.
         Returns the (H, W, 4) float image, or what denoise returns with g_data=True.
         With variance=True the variance-guided filter instead: render_moments of the whole
-        frame + feature_buffers + denoise_variance (whose keyword arguments `sigmas` takes)."""
+        frame + feature_buffers + denoise_variance (whose keyword arguments `sigmas` takes).
+        With adaptive=dict(...) as well (render_adaptive's keyword arguments; variance=True
+        only), render_adaptive of the whole frame takes render_moments' place: its per-pixel
+        sample counts in mom give the filter each pixel's own variance of the mean."""
         if self._frame is None:
             raise _native.SptError(2, "params not set (set_params)")
         w, h = self._frame
+        if adaptive is not None:
+            if not variance:
+                raise ValueError("adaptive=... needs variance=True (the filter reads the per-pixel sample counts)")
+            rgba, mom, _ = self.render_adaptive(0, h, 0, w, **adaptive)
+            return self.denoise_variance(rgba.reshape(h, w, 4), self.feature_buffers(), mom, **sigmas)
         if variance:
             rgba, mom = self.render_moments(0, h, 0, w)
             return self.denoise_variance(rgba.reshape(h, w, 4), self.feature_buffers(), mom, **sigmas)
