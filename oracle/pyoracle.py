@@ -102,6 +102,8 @@ def lib():
         L.spo_render_segment_task_stream.restype = u64
         L.spo_generate_spheres.argtypes = [u32, u32, P, P, P, P, P]; L.spo_generate_spheres.restype = u32
         L.spo_init_spheres.argtypes = [u32, P, P, P, P, P]; L.spo_init_spheres.restype = u32
+        L.spo_math_block.argtypes = [ctypes.c_int, u32, u64, P]; L.spo_math_block.restype = ctypes.c_int
+        L.spo_math_digest.argtypes = [ctypes.c_int, u32, u64, P]; L.spo_math_digest.restype = ctypes.c_int
         _lib = L
     return _lib
 
@@ -248,6 +250,26 @@ def scene_state(seed: int) -> int:
 def uniform_draws(seed: int, a: float, b: float, count: int) -> np.ndarray:
     st = ctypes.c_uint64(scene_state(seed))
     return np.array([lib().spo_uniform(ctypes.byref(st), a, b) for _ in range(count)], np.float32)
+
+
+MATH_BLOCK = 1 << 20  # SPO_MATH_BLOCK
+
+
+def math_block(op: int, first: int, count: int) -> np.ndarray:
+    """Result bits of scalar primitive `op` (SPO_MATH_*) on the input patterns
+    first ... first + count - 1 (mod 2^32)."""
+    out = np.empty(count, np.uint32)
+    if lib().spo_math_block(op, first, count, _p(out)) != 0:
+        raise ValueError(f"spo_math_block({op}, {first:#x}, {count})")
+    return out
+
+
+def math_digest(op: int, first: int, count: int) -> np.ndarray:
+    """One digest per block of 2^20 of those patterns (spt_oracle.h)."""
+    out = np.empty((count + MATH_BLOCK - 1) // MATH_BLOCK, np.uint64)
+    if lib().spo_math_digest(op, first, count, _p(out)) != 0:
+        raise ValueError(f"spo_math_digest({op}, {first:#x}, {count})")
+    return out
 
 
 def primary_rays(frame: Frame, xy, seed: int) -> np.ndarray:

@@ -247,11 +247,12 @@ static inline uint8_t f2u8(float v)
     if (!(v > -2147483648.0f && v < 2147483648.0f)) return 0;
     return (uint8_t)(int32_t)v;
 }
+static inline uint8_t gamma_byte(float c) { return f2u8(roundf(sqrtf(c / 255.f) * 255.f)); }
 static inline void write_pixel(uint8_t *g, v4 c)
 {
-    g[0] = f2u8(roundf(sqrtf(c.x / 255.f) * 255.f));
-    g[1] = f2u8(roundf(sqrtf(c.y / 255.f) * 255.f));
-    g[2] = f2u8(roundf(sqrtf(c.z / 255.f) * 255.f));
+    g[0] = gamma_byte(c.x);
+    g[1] = gamma_byte(c.y);
+    g[2] = gamma_byte(c.z);
 }
 void spo_write_pixel(const float c[4], uint8_t out[3]) { write_pixel(out, ld4w(c)); }
 
@@ -355,9 +356,10 @@ static inline int no_tir(float r, float c)
 {
     return r * sqrtf(1.f - c * c) < 1.f;
 }
+static inline float refract_k(float r, float c) { return r * c - sqrtf(1.f - r * r * (1.f - c * c)); }
 static inline v4 refract_dir(v4 d, v4 n, float r, float c)
 {
-    float k = r * c - sqrtf(1.f - r * r * (1.f - c * c));
+    float k = refract_k(r, c);
     return vnorm(vadd(vmul(d, r), vmul(n, k)));
 }
 
@@ -879,4 +881,70 @@ uint32_t spo_init_spheres(uint32_t seed, float *centers, float *radii, float *co
     }
     fuzz[2] = 0.0f;
     return 10;
+}
+
+/* ------------------------------------------------------------------------- */
+/* The scalar primitives over whole input domains (tests/test_gpu_math_sweep.py): */
+/* the literal definitions above, nothing shortened, against which the device's  */
+/* shortened forms (spt_device.h) are swept.                                     */
+/* ------------------------------------------------------------------------- */
+static inline uint32_t result_bits(float r)
+{
+    uint32_t u;
+    if (r != r) return 0x7FC00000u;
+    memcpy(&u, &r, 4);
+    return u;
+}
+
+/* the result bits of op on input pattern u: NaN results canonical, bytes zero-extended */
+static inline uint32_t math_eval(int op, uint32_t u)
+{
+    const float nAir = 1.0f, nGlass = 1.5f; /* sample_refractive's */
+    float x;
+    memcpy(&x, &u, 4);
+    switch (op) {
+    case SPO_MATH_SQRT: return result_bits(sqrtf(x));
+    case SPO_MATH_POW5: return result_bits(powf(x, 5.f));
+    case SPO_MATH_UNI_M1_1: return result_bits(spo_uniform_u32(u, -1.f, 1.f));
+    case SPO_MATH_UNI_H: return result_bits(spo_uniform_u32(u, -0.5f, 0.5f));
+    case SPO_MATH_UNI_0_1: return result_bits(spo_uniform_u32(u, 0.f, 1.f));
+    case SPO_MATH_REFR_AG: return result_bits(no_tir(nAir / nGlass, x) ? refract_k(nAir / nGlass, x) : -1e30f);
+    case SPO_MATH_REFR_GA: return result_bits(no_tir(nGlass / nAir, x) ? refract_k(nGlass / nAir, x) : -1e30f);
+    case SPO_MATH_GAMMA: return gamma_byte(x);
+    case SPO_MATH_F2U8: return f2u8(x);
+    default: return 0;
+    }
+}
+
+static int math_op_ok(int op)
+{
+    return op == SPO_MATH_SQRT || (op >= SPO_MATH_POW5 && op <= SPO_MATH_F2U8);
+}
+
+int spo_math_block(int op, uint32_t first, uint64_t count, uint32_t *out)
+{
+    if (!math_op_ok(op) || count > ((uint64_t)1 << 32) || !out) return 1;
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < (int64_t)count; ++i) out[i] = math_eval(op, first + (uint32_t)i);
+    return 0;
+}
+
+/* digest[k], k < ceil(count / 2^20): the wrapping sum of fmix64(u << 32 | result) over
+ * block k's input patterns u = first + (k << 20) + i */
+int spo_math_digest(int op, uint32_t first, uint64_t count, uint64_t *digest)
+{
+    const int64_t blocks = (int64_t)((count + SPO_MATH_BLOCK - 1) / SPO_MATH_BLOCK);
+    if (!math_op_ok(op) || count == 0 || count > ((uint64_t)1 << 32) || !digest) return 1;
+#pragma omp parallel for schedule(dynamic, 4)
+    for (int64_t k = 0; k < blocks; ++k) {
+        const uint64_t base = (uint64_t)k * SPO_MATH_BLOCK;
+        const uint64_t n = count - base < SPO_MATH_BLOCK ? count - base : SPO_MATH_BLOCK;
+        uint64_t sum = 0;
+        for (uint64_t i = 0; i < n; ++i) {
+            const uint32_t u = first + (uint32_t)(base + i);
+            sum += fmix64(((uint64_t)u << 32) | math_eval(op, u));
+        }
+        digest[k] = sum;
+    }
+    return 0;
 }

@@ -164,6 +164,32 @@ uint32_t spo_generate_spheres(uint32_t seed, uint32_t cap, float *centers, float
 uint32_t spo_init_spheres(uint32_t seed, float *centers, float *radii, float *colors,
                           uint8_t *materials, float *fuzz);
 
+/* The scalar primitives over consecutive uint32 input patterns [first, first + count),
+ * count <= 2^32, by their literal definitions: sqrtf, glibc's powf(x, 5.f),
+ * spo_uniform_u32 on the three ranges in use, the refraction scalar of
+ * sample_refractive for air->glass and glass->air (-1e30f where no_tir fails),
+ * spo_write_pixel's byte and the x86 float -> uint8_t conversion.  The op codes are those
+ * of tests/cpp/spt_mathsweep.hip (SQRT_POS and SQRT_RAW are device forms only).
+ * spo_math_block writes the result bits (any NaN as 0x7FC00000, a byte zero-extended);
+ * spo_math_digest one wrapping 64-bit sum of fmix64(u << 32 | bits) per block of 2^20
+ * patterns.  Threaded with OpenMP (OMP_NUM_THREADS).  Return 0, or 1 on a bad argument. */
+enum {
+    SPO_MATH_SQRT = 0,
+    SPO_MATH_SQRT_POS = 1,
+    SPO_MATH_SQRT_RAW = 2,
+    SPO_MATH_POW5 = 3,
+    SPO_MATH_UNI_M1_1 = 4,
+    SPO_MATH_UNI_H = 5,
+    SPO_MATH_UNI_0_1 = 6,
+    SPO_MATH_REFR_AG = 7,
+    SPO_MATH_REFR_GA = 8,
+    SPO_MATH_GAMMA = 9,
+    SPO_MATH_F2U8 = 10
+};
+#define SPO_MATH_BLOCK ((uint64_t)1 << 20)
+int spo_math_block(int op, uint32_t first, uint64_t count, uint32_t *out);
+int spo_math_digest(int op, uint32_t first, uint64_t count, uint64_t *digest);
+
 #ifdef __cplusplus
 }
 #endif
