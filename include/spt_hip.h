@@ -661,6 +661,95 @@ SPT_API int spt_render_adaptive_dev(spt_ctx *ctx, uint32_t yBegin, uint32_t yEnd
                                     void *d_rgba /*nullable*/, void *d_rgb8 /*nullable*/, void *d_mom /*nullable*/,
                                     uint64_t *info /*nullable*/, void *stream);
 
+/* ---- temporal accumulation: reproject the last frame's colour and moments ---------------
+ * The temporal part of Schied et al. 2017 (SVGF): each pixel's first hit is reprojected into
+ * the previous frame, the history found there is blended with this frame by sample counts,
+ * and the result is the next frame's history.  It needs no scene, camera or params; the
+ * cameras are arguments.  The library holds no state: the caller keeps (out_rgba, out_mom,
+ * feat, ids) and the camera as the next frame's history.
+ * The image is width x height pixels, row-major, p = y * width + x.
+ *   rgba  float4 per pixel, as the renders write it; w passes through.
+ *   mom   float4 per pixel as spt_render_moments and spt_render_adaptive write it: {m1, m2,
+ *         var, n}; n is the sample count.
+ *   feat  8 floats per pixel as spt_render_features writes them: {alb.rgb, cov}, {nrm.xyz, dep}.
+ *   ids   one uint32 per pixel as spt_render_features writes it: sample 0's sphere.
+ *   hist_rgba, hist_mom, hist_feat, hist_ids  the same four of the previous frame (hist_rgba
+ *         and hist_mom: a previous call's outputs, or a first frame's own rgba and mom); all
+ *         four, or all NULL (no history: prev_view and prev_eye are then not read).
+ *   out_mom has mom's layout, the one spt_denoise_var reads: {m1, m2, var, n'}; n' is the
+ *         accumulated sample count and may be fractional.
+ * Everything is fp32, one rounding per operation written, no contraction, IEEE division and
+ * square root.  M is view, E is eye, Ep is prev_eye, Minv = spt_temporal_inverse(prev_view).
+ * Per pixel p = (x, y):
+ *   z   = dep / cov if cov > 0, else +0                   (the same for history pixels: zq)
+ *   vx  = -1.0f + 2.0f * ((float)x / (float)height)       (the render's own: x over the height,
+ *   vy  = -1.0f + 2.0f * ((float)y / (float)width)         y over the width; the jitter is
+ *                                                          uniform(-1, 1), so the pixel's centre
+ *                                                          is at integer x, y)
+ *   r_i = (M[4i] * vx + M[4i+1] * vy) + M[4i+2]           i = 0, 1, 2
+ *   d   = Normalize(r)                                    (the render's: r / sqrt(|r|^2), lane-wise)
+ *   cov > 0:  P = E + d * z;  w = P - Ep;  L = sqrtf((w.x*w.x + w.y*w.y) + w.z*w.z)
+ *   else:     w = d                                       (the sky: a point at infinity, it
+ *                                                          follows the rotation only)
+ *   q_i = (Minv[3i] * w.x + Minv[3i+1] * w.y) + Minv[3i+2] * w.z
+ *   a = q.x / q.z;  b = q.y / q.z
+ *   fx = ((a + 1.0f) * 0.5f) * (float)height;  fy = ((b + 1.0f) * 0.5f) * (float)width
+ *   static rule: if the nine used entries of view and prev_view (rows 0..2 x columns 0..2) and
+ *     the xyz of eye and prev_eye all compare equal (==), then fx = (float)x, fy = (float)y and
+ *     q.z counts as positive (the arithmetic above returns the pixel's own place only to
+ *     within a few 1e-6).
+ *   history is sought iff q.z > 0 && fx > -1 && fx < width && fy > -1 && fy < height   (NaN fails)
+ *   x0 = floorf(fx);  tx = fx - x0;  y0 = floorf(fy);  ty = fy - y0
+ *   taps, j outer, i inner, i, j in {0, 1}: the tap pixel t = (x0 + i, y0 + j),
+ *     wt = (i ? tx : 1.0f - tx) * (j ? ty : 1.0f - ty)
+ *   a tap is taken iff: t lies inside the image;  wt > 0;  hist_mom_t.w > 0;  hist_rgba_t.rgb
+ *     and hist_mom_t.x, .y, .w are finite;  hist_ids_t == ids_p;
+ *     tol_normal == +inf, or with dn = hist_nrm_t - nrm_p:
+ *       (dn.x*dn.x + dn.y*dn.y) + dn.z*dn.z <= tol_normal;
+ *     cov_p > 0 is false, or tol_depth == +inf, or with dz = zq_t - L, lim = tol_depth * L:
+ *       dz*dz <= lim*lim
+ *   a taken tap adds, all sums starting at +0 and written acc = acc + wt * v:
+ *     ws += wt;  hc.c += wt * hist_rgba_t.c;  h1 += wt * hist_mom_t.x;  h2 += wt * hist_mom_t.y;
+ *     hn += wt * hist_mom_t.w
+ *   ws > 0:  hc.c /= ws;  h1 /= ws;  h2 /= ws;  nh = fminf(hn / ws, max_history);  nc = mom_p.w
+ *            n' = nh + nc;  alpha = nc / n'
+ *            out.c = hc.c + (rgba_p.c - hc.c) * alpha;  m1 = h1 + (mom_p.x - h1) * alpha;
+ *            m2 = h2 + (mom_p.y - h2) * alpha;  dd = m2 - m1 * m1;  var = dd < 0 ? +0 : dd
+ *            out_rgba_p = {out.rgb, rgba_p.w};  out_mom_p = {m1, m2, var, n'}
+ *   else:    out_rgba_p = rgba_p;  out_mom_p = mom_p      (bits and all)
+ * The outputs are the inputs, bit for bit, where no history is given, where any of the
+ * pixel's rgba.rgb, its four mom lanes or its eight feat lanes is not finite, and where
+ * mom_p.w > 0 is false.
+ * tol_normal and tol_depth must be >= 0 (+inf switches the test off); max_history must be
+ * > 0 (+inf: no cap).  They use member 0 of a multi-device context, end a resident
+ * render-service session first and leave spt_stats and the sample workspaces untouched.
+ * SPT_ERR_ARG, before anything is launched and with the outputs untouched, for a null
+ * context, input (view and eye too) or output, some but not all history pointers null, a
+ * tolerance that is NaN or negative, a max_history that is NaN or not > 0, with a history a
+ * null prev_view or prev_eye or a prev_view that spt_temporal_inverse rejects, width x
+ * height >= 2^31, or an output that overlaps any input or the other output.  width == 0 or
+ * height == 0 is SPT_OK and touches nothing. */
+/* host only, no device: the fp32 inverse of view's upper-left 3x3 (rows 0..2, columns 0..2;
+ * row 3 and column 3 are not read), computed in double and rounded once per entry, row-major;
+ * SPT_ERR_ARG for a non-finite entry or a determinant that is not finite and != 0 */
+SPT_API int spt_temporal_inverse(const float view[16], float inv9[9]);
+/* device pointers, asynchronous on `stream` (NULL = default stream); the cameras are read
+ * before the call returns */
+SPT_API int spt_temporal_async(spt_ctx *ctx, uint32_t width, uint32_t height, const void *d_rgba, const void *d_mom,
+                               const void *d_feat, const void *d_ids, const float view[16], const float eye[4],
+                               const void *d_hist_rgba /*nullable*/, const void *d_hist_mom /*nullable*/,
+                               const void *d_hist_feat /*nullable*/, const void *d_hist_ids /*nullable*/,
+                               const float prev_view[16] /*nullable*/, const float prev_eye[4] /*nullable*/,
+                               float tol_normal, float tol_depth, float max_history, void *d_out_rgba, void *d_out_mom,
+                               void *stream);
+/* host pointers, blocking; allocates and frees its own device buffers, as spt_denoise does */
+SPT_API int spt_temporal(spt_ctx *ctx, uint32_t width, uint32_t height, const float *rgba, const float *mom,
+                         const float *feat, const uint32_t *ids, const float view[16], const float eye[4],
+                         const float *hist_rgba /*nullable*/, const float *hist_mom /*nullable*/,
+                         const float *hist_feat /*nullable*/, const uint32_t *hist_ids /*nullable*/,
+                         const float prev_view[16] /*nullable*/, const float prev_eye[4] /*nullable*/, float tol_normal,
+                         float tol_depth, float max_history, float *out_rgba, float *out_mom);
+
 SPT_API int spt_get_stats(spt_ctx *ctx, spt_stats *out);
 SPT_API int spt_reset_stats(spt_ctx *ctx);
 

@@ -163,6 +163,9 @@ def lib() -> ctypes.CDLL:
         "spt_denoise_var": ([P, u32, u32, P, P, P, f32, f32, f32, f32, f32, u32, P, P, P], I),
         "spt_render_adaptive": ([P, u32, u32, u32, u32, u32, u32, u32, f32, f32, P, P, P, P], I),
         "spt_render_adaptive_dev": ([P, u32, u32, u32, u32, u32, u32, u32, f32, f32, P, P, P, P, P], I),
+        "spt_temporal_inverse": ([P, P], I),
+        "spt_temporal_async": ([P, u32, u32, P, P, P, P, P, P, P, P, P, P, P, P, f32, f32, f32, P, P, P], I),
+        "spt_temporal": ([P, u32, u32, P, P, P, P, P, P, P, P, P, P, P, P, f32, f32, f32, P, P], I),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

@@ -17,13 +17,6 @@ constexpr uint32_t kMaxLevels = 8;
 inline uint64_t scratch_planes(uint32_t levels) { return std::min<uint32_t>(levels - 1u, 2u); }
 inline uint64_t scratch_bytes(uint64_t npix, uint32_t levels) { return scratch_planes(levels) * npix * sizeof(float4); }
 
-inline bool overlaps(const void *a, uint64_t na, const void *b, uint64_t nb)
-{
-    if (!a || !b || !na || !nb) return false;
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + nb && b0 < a0 + na;
-}
-
 // One call of either form, as its entry point received it: host pointers for the blocking
 // forms, device pointers for the async ones.
 struct DenoiseCall {

@@ -14,6 +14,7 @@
 //   spt_moments.cpp  per-pixel sample moments (spt_render_moments[_async])
 //   spt_adaptive.cpp adaptive sampling (spt_render_adaptive[_dev]); spt_adaptive.h is the tile plan
 //                    it shares with spt_adaptive.hip and the host check
+//   spt_temporal.cpp temporal accumulation (spt_temporal_inverse, spt_temporal[_async])
 //   spt_staging.cpp  the device staging of their blocking forms; spt_staging.h is its
 //                    HIP-free half (the plan: chunk size, offsets, total)
 // The context owns the device copy of the reference's global state (scene SoA, camera,
@@ -63,6 +64,15 @@ inline const char *env_var(const char *name)
 inline size_t band_offset(uint32_t W, uint32_t H, uint32_t yE, uint32_t xB)
 {
     return ((size_t)(H - yE) * W + xB) * 3;
+}
+
+// Two byte ranges share a byte (the denoiser's and the temporal accumulation's checks of an
+// output against the inputs; a null pointer or an empty range overlaps nothing)
+inline bool overlaps(const void *a, uint64_t na, const void *b, uint64_t nb)
+{
+    if (!a || !b || !na || !nb) return false;
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + nb && b0 < a0 + na;
 }
 
 extern thread_local std::string g_thread_error;

@@ -619,4 +619,25 @@ hipError_t launch_denoise_level(const DenoiseArgs &a, bool var, hipStream_t s);
 // spp} of the samples' luminance in sample order, p the local row-major pixel.
 hipError_t launch_moments(const FoldArgs &f, float4 *mom, hipStream_t s);
 
+// ---- temporal accumulation (spt_temporal.hip; spt_temporal[_async]) --------------------
+// One launch over a width x height image: this frame's rgba, mom, feat (two float4 per
+// pixel) and ids, the history's four (all null: no history, the outputs are copies), and
+// the two outputs.  m and e are this frame's camera (the nine used entries of view, rows
+// 0..2 x columns 0..2, and the eye), minv and ep the previous one's (spt_temporal_inverse of
+// its view, and its eye); fw and fh the width and height as floats; is_static: the two
+// cameras compare equal, the static rule holds.  tiles_x is the launch's own.
+struct TemporalArgs {
+    const float4 *rgba, *mom, *feat;
+    const uint32_t *ids;
+    const float4 *h_rgba, *h_mom, *h_feat;
+    const uint32_t *h_ids;
+    float4 *out_rgba, *out_mom;
+    uint32_t width, height, tiles_x;
+    float fw, fh;
+    float m[9], e[3], minv[9], ep[3];
+    float tol_normal, tol_depth, max_history;
+    uint32_t is_static;
+};
+hipError_t launch_temporal(TemporalArgs a, hipStream_t s);
+
 }  // namespace spt

@@ -1,6 +1,6 @@
 // spt_staging.h -- device staging of the blocking queries (spt_cast_rays, spt_primary_hits,
 // spt_trace_rays, spt_render_features, spt_denoise, spt_denoise_var, spt_render_moments,
-// spt_render_adaptive): one
+// spt_render_adaptive, spt_temporal): one
 // device allocation cut into the arrays of a chunk of the call's items (rays, rows of
 // pixels, or the whole image), which the call copies in, launches over and copies out chunk
 // by chunk.  One plan per form (the two filters share denoise_plan: the variance-guided one
@@ -99,6 +99,14 @@ inline StagingPlan adaptive_staging_plan(size_t npix, size_t frame_bytes, bool r
 {
     const StagingArray a[3] = {{npix * 16, rgba}, {npix * 16, mom}, {frame_bytes, g_data, true}};
     return staging_plan(a, 3, 1, StagingItems::kAll);
+}
+// spt_temporal, per pixel of the whole image: this frame's {rgba, mom, feat} (16 + 16 + 32
+// bytes, three planes one after the other) and ids in, the history's same two arrays (absent
+// without a history), then {out_rgba, out_mom} out (two planes)
+inline StagingPlan temporal_plan(size_t npix, bool hist)
+{
+    const StagingArray a[5] = {{64}, {4}, {64, hist}, {4, hist}, {32}};
+    return staging_plan(a, 5, npix, StagingItems::kAll);
 }
 
 // The allocation of a plan, for one blocking call on one stream (spt_staging.cpp).  A call

@@ -498,6 +498,62 @@ class Context:
                                                           _p(info), ctypes.c_void_p(stream or None)))
         return {"samples": int(info[0]), "passes": int(info[1])}
 
+    def temporal(self, rgba, mom, feat, ids, view, eye, history=None, prev_view=None, prev_eye=None, tol_normal=0.25,
+                 tol_depth=0.1, max_history=64.0):
+        """Temporal accumulation of include/spt_hip.h "temporal accumulation" on the device
+        (spt_temporal): this frame's rgba ((H, W, 4), or the current frame as (W * H, 4)), mom
+        (what render_moments or render_adaptive returns), feat and ids (what
+        render_features(ids=True) returns) and its camera, blended with `history`, the tuple
+        (rgba, mom, feat, ids) of the previous frame (rgba and mom: the previous call's
+        outputs, or a first frame's own), seen through prev_view from prev_eye.  Without a
+        history the outputs are copies.  Returns (out_rgba, out_mom) in rgba's and mom's
+        shapes; keep them with feat, ids and the camera as the next frame's history."""
+        rgba, feat, w, h = self._denoise_inputs(rgba, feat)
+        n = w * h
+
+        def arr(a, dtype, per, what):
+            a = np.ascontiguousarray(a, dtype)
+            if a.size != n * per:
+                raise ValueError(f"{what}: expected {per} value(s) for each of {w} x {h} pixels, got shape {a.shape}")
+            return a
+
+        mom = arr(mom, np.float32, 4, "mom")
+        ids = arr(ids, np.uint32, 1, "ids")
+        cam = [_view16(view), _eye4(eye), None, None]
+        hist = [None] * 4
+        if history is not None:
+            if prev_view is None or prev_eye is None:
+                raise ValueError("history needs prev_view and prev_eye")
+            h_rgba, h_mom, h_feat, h_ids = history
+            hist = [arr(h_rgba, np.float32, 4, "history rgba"), arr(h_mom, np.float32, 4, "history mom"),
+                    arr(h_feat, np.float32, 8, "history feat"), arr(h_ids, np.uint32, 1, "history ids")]
+            cam[2:] = [_view16(prev_view), _eye4(prev_eye)]
+        out, out_mom = np.zeros_like(rgba), np.zeros_like(mom)
+        ptr = lambda a: None if a is None else _p(a)  # noqa: E731
+        self._check(_native.lib().spt_temporal(self._h, w, h, _p(rgba), _p(mom), _p(feat), _p(ids), _p(cam[0]), _p(cam[1]),
+                                               ptr(hist[0]), ptr(hist[1]), ptr(hist[2]), ptr(hist[3]), ptr(cam[2]),
+                                               ptr(cam[3]), tol_normal, tol_depth, max_history, _p(out), _p(out_mom)))
+        return out, out_mom
+
+    def temporal_async(self, width, height, d_rgba, d_mom, d_feat, d_ids, view, eye, d_hist=None, prev_view=None,
+                       prev_eye=None, tol_normal=0.25, tol_depth=0.1, max_history=64.0, d_out_rgba=0, d_out_mom=0,
+                       stream=0) -> None:
+        """Device-resident temporal (spt_temporal_async): raw device pointers to this frame's
+        width * height float4 colours, float4 moments, 8 floats of features and uint32 ids per
+        pixel, d_hist the tuple of the previous frame's four pointers (or None), and the two
+        float4 outputs; the cameras are host arrays, read before the call returns.  One launch
+        on `stream` (a hipStream_t; 0 = the default stream)."""
+        cam = [_view16(view), _eye4(eye), None if prev_view is None else _view16(prev_view),
+               None if prev_eye is None else _eye4(prev_eye)]
+        dh = tuple(d_hist) if d_hist is not None else (0, 0, 0, 0)
+        ptr = lambda a: None if a is None else _p(a)  # noqa: E731
+        self._check(_native.lib().spt_temporal_async(
+            self._h, int(width), int(height), ctypes.c_void_p(d_rgba or None), ctypes.c_void_p(d_mom or None),
+            ctypes.c_void_p(d_feat or None), ctypes.c_void_p(d_ids or None), ptr(cam[0]), ptr(cam[1]),
+            ctypes.c_void_p(dh[0] or None), ctypes.c_void_p(dh[1] or None), ctypes.c_void_p(dh[2] or None),
+            ctypes.c_void_p(dh[3] or None), ptr(cam[2]), ptr(cam[3]), tol_normal, tol_depth, max_history,
+            ctypes.c_void_p(d_out_rgba or None), ctypes.c_void_p(d_out_mom or None), ctypes.c_void_p(stream or None)))
+
     def render_denoised(self, variance=False, adaptive=None, **sigmas) -> np.ndarray:
         """The current frame rendered, its feature buffers, and the frame filtered by denoise
         (whose keyword arguments `sigmas` takes): render_frame + feature_buffers + denoise.
@@ -573,6 +629,63 @@ def rows_count(yB, yE, strip, parts, part) -> int:
     r = ctypes.c_uint32(0)
     _native.check(_native.lib().spt_rows_count(yB, yE, strip, parts, part, ctypes.byref(r)))
     return r.value
+
+
+def _view16(view) -> np.ndarray:
+    return np.ascontiguousarray(np.asarray(view, np.float32).reshape(16))
+
+
+def _eye4(eye) -> np.ndarray:
+    """An eye of 3 or 4 floats as the 4 the C ABI reads."""
+    e = np.asarray(eye, np.float32).reshape(-1)
+    if e.size not in (3, 4):
+        raise ValueError(f"eye: expected 3 or 4 floats, got {e.size}")
+    return np.ascontiguousarray(np.concatenate([e[:3], np.zeros(1, np.float32)]))
+
+
+def temporal_inverse(view) -> np.ndarray:
+    """The (3, 3) float32 inverse of view's upper-left 3x3 as Context.temporal uses it for the
+    previous camera (spt_temporal_inverse): computed in double, rounded once per entry."""
+    v = _view16(view)
+    out = np.zeros((3, 3), np.float32)
+    _native.check(_native.lib().spt_temporal_inverse(_p(v), _p(out)))
+    return out
+
+
+class TemporalAccumulator:
+    """A preview that keeps its samples while the camera moves: every frame(view, eye) renders
+    width x height at spp samples with a seed of its own, accumulates it against the stored
+    history (Context.temporal, whose keyword arguments `temporal_kwargs` takes) and stores the
+    accumulated, unfiltered result as the next frame's history.  The context's scene must be
+    set; camera and params are set by every frame."""
+
+    def __init__(self, ctx: Context, width, height, spp, bounces, seed=1, sky=INIT_COLOR, **temporal_kwargs):
+        self.ctx, self.width, self.height, self.spp, self.bounces = ctx, int(width), int(height), int(spp), int(bounces)
+        self.seed, self.sky, self.kwargs = int(seed), sky, temporal_kwargs
+        self.reset()
+
+    def reset(self) -> None:
+        """Forget the history and start the seeds again: the next frame passes through."""
+        self.frame_index = 0
+        self._history = None  # ((rgba, mom, feat, ids), view, eye)
+
+    def frame(self, view, eye, denoise=None) -> np.ndarray:
+        """The accumulated (H, W, 4) image of the next frame seen through `view` from `eye`;
+        with denoise=dict(...) (denoise_variance's keyword arguments, {} for its defaults)
+        that filter's result on the accumulated colour and moments instead.  The history
+        kept is the unfiltered one either way."""
+        c, w, h = self.ctx, self.width, self.height
+        c.set_camera(view, _eye4(eye), self.sky)
+        c.set_params(w, h, self.spp, self.bounces, self.seed + self.frame_index)
+        rgba, mom = c.render_moments(0, h, 0, w)
+        feat, ids = c.render_features(0, h, 0, w, ids=True)
+        hist, pv, pe = self._history if self._history is not None else (None, None, None)
+        out, out_mom = c.temporal(rgba.reshape(h, w, 4), mom, feat, ids, view, eye, hist, pv, pe, **self.kwargs)
+        self._history = ((out, out_mom, feat, ids), _view16(view).copy(), _eye4(eye))
+        self.frame_index += 1
+        if denoise is not None:
+            return c.denoise_variance(out, feat, out_mom, **denoise)
+        return out
 
 
 class Globals:
