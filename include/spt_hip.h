@@ -749,6 +749,51 @@ SPT_API int spt_temporal(spt_ctx *ctx, uint32_t width, uint32_t height, const fl
                          const float *hist_feat /*nullable*/, const uint32_t *hist_ids /*nullable*/,
                          const float prev_view[16] /*nullable*/, const float prev_eye[4] /*nullable*/, float tol_normal,
                          float tol_depth, float max_history, float *out_rgba, float *out_mom);
+/* ---- temporal accumulation under moving spheres -------------------------------------------
+ * The same call with a motion table: the spheres are uniformly coloured, so a rigid motion is
+ * a translation of the centre and a change of radius (a rotation is invisible).
+ *   motion  n_spheres records of 8 floats, 32 bytes each, {C.x, C.y, C.z, r, Cp.x, Cp.y, Cp.z,
+ *           rp}: this frame's centre and radius, then the previous frame's; indexed by the
+ *           sphere index that ids carries.  The caller keeps the spheres' count and order the
+ *           same across the two frames; the call cannot check that.  A device table is 16-byte
+ *           aligned, as every other device array of the call.
+ * Everything under "temporal accumulation" above stands, but for the lines that form w, L and
+ * the static rule.  With hit = cov > 0, id = ids_p and P = E + d * z as there, and
+ * {C, r, Cp, rp} = motion[id]:
+ *   mv = hit && id < n_spheres && !(C.x == Cp.x && C.y == Cp.y && C.z == Cp.z && r == rp)
+ *   mv:   s = rp / r                                       (IEEE division)
+ *         u = P - C;  Pp_i = Cp_i + u_i * s                (the product rounded, then the sum)
+ *         history is not sought unless Pp.x, Pp.y, Pp.z are all finite
+ *         w = Pp - Ep;  L = sqrtf((w.x*w.x + w.y*w.y) + w.z*w.z)
+ *   !mv:  w, L as above (P - Ep on a hit, d on the sky)
+ *   static rule: it applies to a pixel iff the cameras compare equal as above and !mv for
+ *     that pixel (Cp + (P - C) does not return P in fp32, hence "unmoved" is a rule too).
+ * A pixel with !mv -- the sky, an id >= n_spheres (the miss sentinel, or any other value), a
+ * sphere whose record did not change -- gets spt_temporal's output, bit for bit; so does every
+ * pixel of a table in which nothing moved, and of n_spheres == 0 (the table is then not read
+ * and may be NULL).  No record is read for id >= n_spheres.  A record with r == 0, a
+ * non-finite entry or radii of opposite sign has no case of its own: s or Pp is not finite and
+ * the pixel passes through, or the taps fail their tests.  The id, normal and depth tests are
+ * the same: the normal does not change under a translation and a positive scale, and the depth
+ * test compares zq with the new L.
+ * Errors, service, statistics, workspaces and member 0 as for spt_temporal; SPT_ERR_ARG as
+ * well for n_spheres > 0 with a null table and for an output that overlaps the table. */
+SPT_API int spt_temporal_motion_async(spt_ctx *ctx, uint32_t width, uint32_t height, const void *d_rgba,
+                                      const void *d_mom, const void *d_feat, const void *d_ids, const float view[16],
+                                      const float eye[4], const void *d_hist_rgba /*nullable*/,
+                                      const void *d_hist_mom /*nullable*/, const void *d_hist_feat /*nullable*/,
+                                      const void *d_hist_ids /*nullable*/, const float prev_view[16] /*nullable*/,
+                                      const float prev_eye[4] /*nullable*/, const void *d_motion /*nullable*/,
+                                      uint32_t n_spheres, float tol_normal, float tol_depth, float max_history,
+                                      void *d_out_rgba, void *d_out_mom, void *stream);
+/* host pointers, blocking; the table is staged with the images */
+SPT_API int spt_temporal_motion(spt_ctx *ctx, uint32_t width, uint32_t height, const float *rgba, const float *mom,
+                                const float *feat, const uint32_t *ids, const float view[16], const float eye[4],
+                                const float *hist_rgba /*nullable*/, const float *hist_mom /*nullable*/,
+                                const float *hist_feat /*nullable*/, const uint32_t *hist_ids /*nullable*/,
+                                const float prev_view[16] /*nullable*/, const float prev_eye[4] /*nullable*/,
+                                const float *motion /*nullable*/, uint32_t n_spheres, float tol_normal, float tol_depth,
+                                float max_history, float *out_rgba, float *out_mom);
 
 SPT_API int spt_get_stats(spt_ctx *ctx, spt_stats *out);
 SPT_API int spt_reset_stats(spt_ctx *ctx);

@@ -9,12 +9,12 @@ from .scene import (DIFFUSE, REFLECTIVE, REFRACTIVE, SKYBOX, INIT_COLOR, Scene, 
                     generate_spheres, generate_stress, init_spheres)
 from .renderer import (Context, Globals, MakeRenderSegmentData, RenderImage, RenderImageParallelMain,  # noqa: F401
                        RenderSegment, RenderSegmentData, RenderSegmentTask, SaveImage, TemporalAccumulator,
-                       denoise_scratch_bytes, rows_count, sample_state, temporal_inverse)
+                       denoise_scratch_bytes, rows_count, sample_state, sphere_motion, temporal_inverse)
 
 __all__ = [
     "SaveImage", "MODE_SEGMENT", "MODE_TASK", "SptError", "build", "lib", "Scene", "camera_basis", "cornell3",
     "generate_spheres", "generate_stress", "init_spheres", "Context", "Globals", "MakeRenderSegmentData",
     "RenderImage", "RenderImageParallelMain", "RenderSegment", "RenderSegmentData", "RenderSegmentTask",
     "rows_count", "sample_state", "denoise_scratch_bytes", "DIFFUSE", "REFLECTIVE", "REFRACTIVE", "SKYBOX", "INIT_COLOR",
-    "TemporalAccumulator", "temporal_inverse",
+    "TemporalAccumulator", "temporal_inverse", "sphere_motion",
 ]

@@ -166,6 +166,8 @@ def lib() -> ctypes.CDLL:
         "spt_temporal_inverse": ([P, P], I),
         "spt_temporal_async": ([P, u32, u32, P, P, P, P, P, P, P, P, P, P, P, P, f32, f32, f32, P, P, P], I),
         "spt_temporal": ([P, u32, u32, P, P, P, P, P, P, P, P, P, P, P, P, f32, f32, f32, P, P], I),
+        "spt_temporal_motion_async": ([P, u32, u32, P, P, P, P, P, P, P, P, P, P, P, P, P, u32, f32, f32, f32, P, P, P], I),
+        "spt_temporal_motion": ([P, u32, u32, P, P, P, P, P, P, P, P, P, P, P, P, P, u32, f32, f32, f32, P, P], I),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

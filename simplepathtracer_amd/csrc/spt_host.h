@@ -14,7 +14,8 @@
 //   spt_moments.cpp  per-pixel sample moments (spt_render_moments[_async])
 //   spt_adaptive.cpp adaptive sampling (spt_render_adaptive[_dev]); spt_adaptive.h is the tile plan
 //                    it shares with spt_adaptive.hip and the host check
-//   spt_temporal.cpp temporal accumulation (spt_temporal_inverse, spt_temporal[_async])
+//   spt_temporal.cpp temporal accumulation (spt_temporal_inverse, spt_temporal[_async],
+//                    spt_temporal_motion[_async])
 //   spt_staging.cpp  the device staging of their blocking forms; spt_staging.h is its
 //                    HIP-free half (the plan: chunk size, offsets, total)
 // The context owns the device copy of the reference's global state (scene SoA, camera,

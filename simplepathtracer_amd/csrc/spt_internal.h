@@ -626,6 +626,9 @@ hipError_t launch_moments(const FoldArgs &f, float4 *mom, hipStream_t s);
 // 0..2 x columns 0..2, and the eye), minv and ep the previous one's (spt_temporal_inverse of
 // its view, and its eye); fw and fh the width and height as floats; is_static: the two
 // cameras compare equal, the static rule holds.  tiles_x is the launch's own.
+// The motion variant (spt_temporal_motion[_async]) reads motion as well: n_spheres records
+// of two float4, {C.xyz, r} of this frame and {Cp.xyz, rp} of the previous one, indexed by
+// the pixel's id (null with n_spheres == 0); the plain kernel reads neither field.
 struct TemporalArgs {
     const float4 *rgba, *mom, *feat;
     const uint32_t *ids;
@@ -637,7 +640,9 @@ struct TemporalArgs {
     float m[9], e[3], minv[9], ep[3];
     float tol_normal, tol_depth, max_history;
     uint32_t is_static;
+    const float4 *motion;
+    uint32_t n_spheres;
 };
-hipError_t launch_temporal(TemporalArgs a, hipStream_t s);
+hipError_t launch_temporal(TemporalArgs a, bool motion, hipStream_t s);
 
 }  // namespace spt

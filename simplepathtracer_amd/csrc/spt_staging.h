@@ -102,11 +102,18 @@ inline StagingPlan adaptive_staging_plan(size_t npix, size_t frame_bytes, bool r
 }
 // spt_temporal, per pixel of the whole image: this frame's {rgba, mom, feat} (16 + 16 + 32
 // bytes, three planes one after the other) and ids in, the history's same two arrays (absent
-// without a history), then {out_rgba, out_mom} out (two planes)
-inline StagingPlan temporal_plan(size_t npix, bool hist)
+// without a history), then {out_rgba, out_mom} out (two planes); spt_temporal_motion's table
+// of motion_bytes bytes (32 per sphere, not per pixel) follows them as array 5, absent at 0
+inline StagingPlan temporal_plan(size_t npix, bool hist, size_t motion_bytes = 0)
 {
     const StagingArray a[5] = {{64}, {4}, {64, hist}, {4, hist}, {32}};
-    return staging_plan(a, 5, npix, StagingItems::kAll);
+    StagingPlan p = staging_plan(a, 5, npix, StagingItems::kAll);
+    if ((p.present[5] = motion_bytes != 0)) {
+        p.off[5] = p.total;
+        p.bytes[5] = motion_bytes;
+        p.total += round16(motion_bytes);
+    }
+    return p;
 }
 
 // The allocation of a plan, for one blocking call on one stream (spt_staging.cpp).  A call

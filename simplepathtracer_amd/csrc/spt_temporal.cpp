@@ -1,5 +1,6 @@
 // spt_temporal.cpp -- temporal accumulation: spt_temporal_inverse and
-// spt_temporal[_async], the host half of spt_temporal.hip.  Like the denoiser they need no
+// spt_temporal[_async] and spt_temporal_motion[_async] (§4.15: the same call with a table of
+// the spheres' motion), the host half of spt_temporal.hip.  Like the denoiser they need no
 // scene, camera or params, use member 0 of a multi-device context, end a resident service
 // session first, touch neither the statistics nor the sample workspaces and read no candidate
 // lists.  The library keeps no history: the caller passes the last frame's outputs back in.
@@ -42,6 +43,9 @@ struct TemporalCall {
     const float *prev_view, *prev_eye;
     float tol_normal, tol_depth, max_history;
     void *out_rgba, *out_mom;
+    bool with_motion = false;      // the motion entry points: the table below is an argument
+    const void *motion = nullptr;  // n_spheres records of 8 floats (null with n_spheres == 0)
+    uint32_t n_spheres = 0;
 };
 
 // the checks; on SPT_OK with *nothing clear, `a` holds the cameras and the parameters
@@ -51,6 +55,7 @@ int temporal_check(spt_ctx *ctx, const TemporalCall &c, spt::TemporalArgs *a, bo
     if (!c.rgba || !c.mom || !c.feat || !c.ids) return fail(ctx, SPT_ERR_ARG, "null rgba, mom, feat or ids");
     if (!c.view || !c.eye) return fail(ctx, SPT_ERR_ARG, "null view or eye");
     if (!c.out_rgba || !c.out_mom) return fail(ctx, SPT_ERR_ARG, "null out_rgba or out_mom");
+    if (c.n_spheres > 0 && !c.motion) return fail(ctx, SPT_ERR_ARG, "null motion with n_spheres = %u", c.n_spheres);
     const int n_hist = (c.h_rgba != nullptr) + (c.h_mom != nullptr) + (c.h_feat != nullptr) + (c.h_ids != nullptr);
     if (n_hist != 0 && n_hist != 4) return fail(ctx, SPT_ERR_ARG, "%d of the four history pointers are null: all or none", 4 - n_hist);
     const bool hist = n_hist == 4;
@@ -73,9 +78,9 @@ int temporal_check(spt_ctx *ctx, const TemporalCall &c, spt::TemporalArgs *a, bo
         uint64_t n;
         const char *name;
     } outs[2] = {{c.out_rgba, npix * 16u, "out_rgba"}, {c.out_mom, npix * 16u, "out_mom"}},
-      ins[8] = {{c.rgba, npix * 16u, "rgba"}, {c.mom, npix * 16u, "mom"}, {c.feat, npix * 32u, "feat"}, {c.ids, npix * 4u, "ids"},
+      ins[9] = {{c.rgba, npix * 16u, "rgba"}, {c.mom, npix * 16u, "mom"}, {c.feat, npix * 32u, "feat"}, {c.ids, npix * 4u, "ids"},
                 {c.h_rgba, npix * 16u, "hist_rgba"}, {c.h_mom, npix * 16u, "hist_mom"}, {c.h_feat, npix * 32u, "hist_feat"},
-                {c.h_ids, npix * 4u, "hist_ids"}};
+                {c.h_ids, npix * 4u, "hist_ids"}, {c.n_spheres ? c.motion : nullptr, (uint64_t)c.n_spheres * 32u, "motion"}};
     for (const auto &o : outs)
         for (const auto &i : ins)
             if (overlaps(o.p, o.n, i.p, i.n)) return fail(ctx, SPT_ERR_ARG, "%s overlaps %s", o.name, i.name);
@@ -114,7 +119,9 @@ int temporal_launch(spt_ctx *ctx, const TemporalCall &c, spt::TemporalArgs a, hi
     a.h_ids = (const uint32_t *)c.h_ids;
     a.out_rgba = (float4 *)c.out_rgba;
     a.out_mom = (float4 *)c.out_mom;
-    HIP_TRY(ctx, spt::launch_temporal(a, s));
+    a.motion = c.n_spheres ? (const float4 *)c.motion : nullptr;
+    a.n_spheres = c.n_spheres;
+    HIP_TRY(ctx, spt::launch_temporal(a, c.with_motion, s));
     return SPT_OK;
 }
 
@@ -135,7 +142,8 @@ int temporal_run(spt_ctx *ctx, const TemporalCall &c, const hipStream_t *stream)
     const bool hist = c.h_rgba != nullptr;
     const hipStream_t s = ctx->stream;
     Staging st;
-    if (!st.alloc(temporal_plan(npix, hist), s)) return fail(ctx, SPT_ERR_NOMEM, "spt_temporal: %zu bytes of device buffers", st.plan.total);
+    const size_t table = (size_t)c.n_spheres * 32;
+    if (!st.alloc(temporal_plan(npix, hist, table), s)) return fail(ctx, SPT_ERR_NOMEM, "spt_temporal: %zu bytes of device buffers", st.plan.total);
     TemporalCall d = c;
     char *cur = st.at<char>(0), *old = st.at<char>(2), *out = st.at<char>(4);
     d.rgba = cur;
@@ -148,6 +156,8 @@ int temporal_run(spt_ctx *ctx, const TemporalCall &c, const hipStream_t *stream)
     d.h_ids = st.at<uint32_t>(3);
     d.out_rgba = out;
     d.out_mom = out + b16;
+    d.motion = st.at<char>(5);
+    if (table) HIP_TRY(ctx, hipMemcpyAsync((void *)d.motion, c.motion, table, hipMemcpyHostToDevice, s));
     const struct {
         const void *dst, *src;
         size_t n;
@@ -186,6 +196,30 @@ int spt_temporal_async(spt_ctx *ctx, uint32_t width, uint32_t height, const void
     const hipStream_t s = (hipStream_t)stream;
     return temporal_run(ctx, {width, height, d_rgba, d_mom, d_feat, d_ids, view, eye, d_hist_rgba, d_hist_mom, d_hist_feat,
                               d_hist_ids, prev_view, prev_eye, tol_normal, tol_depth, max_history, d_out_rgba, d_out_mom}, &s);
+}
+
+int spt_temporal_motion_async(spt_ctx *ctx, uint32_t width, uint32_t height, const void *d_rgba, const void *d_mom,
+                              const void *d_feat, const void *d_ids, const float view[16], const float eye[4],
+                              const void *d_hist_rgba, const void *d_hist_mom, const void *d_hist_feat,
+                              const void *d_hist_ids, const float prev_view[16], const float prev_eye[4],
+                              const void *d_motion, uint32_t n_spheres, float tol_normal, float tol_depth,
+                              float max_history, void *d_out_rgba, void *d_out_mom, void *stream)
+{
+    const hipStream_t s = (hipStream_t)stream;
+    return temporal_run(ctx, {width, height, d_rgba, d_mom, d_feat, d_ids, view, eye, d_hist_rgba, d_hist_mom, d_hist_feat,
+                              d_hist_ids, prev_view, prev_eye, tol_normal, tol_depth, max_history, d_out_rgba, d_out_mom,
+                              true, d_motion, n_spheres}, &s);
+}
+
+int spt_temporal_motion(spt_ctx *ctx, uint32_t width, uint32_t height, const float *rgba, const float *mom,
+                        const float *feat, const uint32_t *ids, const float view[16], const float eye[4],
+                        const float *hist_rgba, const float *hist_mom, const float *hist_feat, const uint32_t *hist_ids,
+                        const float prev_view[16], const float prev_eye[4], const float *motion, uint32_t n_spheres,
+                        float tol_normal, float tol_depth, float max_history, float *out_rgba, float *out_mom)
+{
+    return temporal_run(ctx, {width, height, rgba, mom, feat, ids, view, eye, hist_rgba, hist_mom, hist_feat, hist_ids,
+                              prev_view, prev_eye, tol_normal, tol_depth, max_history, out_rgba, out_mom, true, motion,
+                              n_spheres}, nullptr);
 }
 
 int spt_temporal(spt_ctx *ctx, uint32_t width, uint32_t height, const float *rgba, const float *mom, const float *feat,

@@ -16,6 +16,14 @@
 // Arithmetic: fp32 without contraction in the definition's order; normalize and div_rn
 // (spt_device.h) and __builtin_sqrtf are the IEEE operations the render uses.
 // Lanes whose pixel lies past the image do nothing.
+//
+// The motion variant (kMotion; spt_temporal_motion[_async]) is the same body
+// with one more gather: the lane's own ids word is loaded with the pixel, and its sphere's
+// 32-byte record {C, r, Cp, rp} with two 16-byte loads right behind it, predicated on
+// id < n_spheres, so they are in flight during the reprojection arithmetic.  ids is coherent
+// within a tile and the table is a few KB, so the gather stays in cache.  A moved sphere's
+// hit point is carried back, Pp = Cp + (P - C) * (rp / r), before it is reprojected; every
+// other pixel takes the plain path, bits and all, and the static rule holds per pixel.
 #include "spt_device.h"
 #include "spt_internal.h"
 
@@ -34,6 +42,7 @@ __device__ __forceinline__ bool finite4(const float4 &v) { return finite3(v.x, v
 
 }  // namespace
 
+template <bool kMotion>
 __global__ __launch_bounds__(kTemporalBlock) void temporal_kernel(TemporalArgs a)
 {
     const uint32_t by = blockIdx.x / a.tiles_x, bx = blockIdx.x - by * a.tiles_x;
@@ -43,8 +52,19 @@ __global__ __launch_bounds__(kTemporalBlock) void temporal_kernel(TemporalArgs a
     const size_t p = (size_t)y * a.width + x;
     const float4 c = a.rgba[p], m = a.mom[p], f0 = a.feat[2u * p], f1 = a.feat[2u * p + 1u];
     float4 oc = c, om = m;  // no history: the pixel passes through, bits and all
+    uint32_t own_id = 0;
+    float4 rec0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), rec1 = rec0;  // an id outside the table: unmoved
+    bool in_table = false;
+    if constexpr (kMotion) {
+        own_id = a.ids[p];
+        in_table = own_id < a.n_spheres;  // the miss sentinel or garbage: nothing is read
+        if (in_table) {
+            rec0 = a.motion[2u * (size_t)own_id];
+            rec1 = a.motion[2u * (size_t)own_id + 1u];
+        }
+    }
     if (a.h_rgba && finite3(c.x, c.y, c.z) && finite4(m) && finite4(f0) && finite4(f1) && m.w > 0.0f) {
-        const uint32_t id = a.ids[p];
+        const uint32_t id = kMotion ? own_id : a.ids[p];
         const bool hit = f0.w > 0.0f;
         const float z = hit ? div_rn(f1.w, f0.w) : 0.0f;
         // the render's own quirk: x over the height, y over the width
@@ -55,9 +75,20 @@ __global__ __launch_bounds__(kTemporalBlock) void temporal_kernel(TemporalArgs a
         const f3 d = normalize(r);
         f3 w = d;  // the sky: a point at infinity, it follows the rotation only
         float L = 0.0f;
+        bool mv = false, seek = true;
         if (hit) {
             const f3 P = add(mk(a.e[0], a.e[1], a.e[2]), mul(d, z));
-            w = sub(P, mk(a.ep[0], a.ep[1], a.ep[2]));
+            f3 from = P;
+            if constexpr (kMotion) {
+                mv = in_table && !(rec0.x == rec1.x && rec0.y == rec1.y && rec0.z == rec1.z && rec0.w == rec1.w);
+                if (mv) {  // the sphere's own frame: the point keeps its place on the sphere
+                    const float sc = div_rn(rec1.w, rec0.w);
+                    const f3 u = sub(P, mk(rec0.x, rec0.y, rec0.z));
+                    from = add(mk(rec1.x, rec1.y, rec1.z), mul(u, sc));
+                    seek = finite3(from.x, from.y, from.z);
+                }
+            }
+            w = sub(from, mk(a.ep[0], a.ep[1], a.ep[2]));
             L = __builtin_sqrtf(lensq(w));
         }
         const float qx = (a.minv[0] * w.x + a.minv[1] * w.y) + a.minv[2] * w.z;
@@ -66,12 +97,12 @@ __global__ __launch_bounds__(kTemporalBlock) void temporal_kernel(TemporalArgs a
         float fx = ((div_rn(qx, qz) + 1.0f) * 0.5f) * a.fh;
         float fy = ((div_rn(qy, qz) + 1.0f) * 0.5f) * a.fw;
         bool front = qz > 0.0f;
-        if (a.is_static) {  // the same camera: the pixel's own place, exactly
+        if (a.is_static && !mv) {  // the same camera, the same sphere: the pixel's own place, exactly
             fx = (float)x;
             fy = (float)y;
             front = true;
         }
-        if (front && fx > -1.0f && fx < a.fw && fy > -1.0f && fy < a.fh) {  // NaN fails
+        if (seek && front && fx > -1.0f && fx < a.fw && fy > -1.0f && fy < a.fh) {  // NaN fails
             const float x0f = __builtin_floorf(fx), y0f = __builtin_floorf(fy);
             const float tx = fx - x0f, ty = fy - y0f;
             const int x0 = (int)x0f, y0 = (int)y0f;  // -1 .. width - 1, -1 .. height - 1
@@ -158,13 +189,16 @@ __global__ __launch_bounds__(kTemporalBlock) void temporal_kernel(TemporalArgs a
     a.out_mom[p] = om;
 }
 
-hipError_t launch_temporal(TemporalArgs a, hipStream_t s)
+hipError_t launch_temporal(TemporalArgs a, bool motion, hipStream_t s)
 {
     a.tiles_x = (a.width + kTemporalTileX - 1u) / kTemporalTileX;
     const uint64_t blocks = (uint64_t)a.tiles_x * ((a.height + kTemporalTileY - 1u) / kTemporalTileY);
     if (blocks == 0) return hipSuccess;
     if (blocks > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
-    hipLaunchKernelGGL(temporal_kernel, dim3((uint32_t)blocks), dim3(kTemporalBlock), 0, s, a);
+    if (motion)
+        hipLaunchKernelGGL(temporal_kernel<true>, dim3((uint32_t)blocks), dim3(kTemporalBlock), 0, s, a);
+    else
+        hipLaunchKernelGGL(temporal_kernel<false>, dim3((uint32_t)blocks), dim3(kTemporalBlock), 0, s, a);
     return hipGetLastError();
 }
 

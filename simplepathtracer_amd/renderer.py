@@ -499,7 +499,7 @@ class Context:
         return {"samples": int(info[0]), "passes": int(info[1])}
 
     def temporal(self, rgba, mom, feat, ids, view, eye, history=None, prev_view=None, prev_eye=None, tol_normal=0.25,
-                 tol_depth=0.1, max_history=64.0):
+                 tol_depth=0.1, max_history=64.0, motion=None):
         """Temporal accumulation of include/spt_hip.h "temporal accumulation" on the device
         (spt_temporal): this frame's rgba ((H, W, 4), or the current frame as (W * H, 4)), mom
         (what render_moments or render_adaptive returns), feat and ids (what
@@ -507,7 +507,9 @@ class Context:
         (rgba, mom, feat, ids) of the previous frame (rgba and mom: the previous call's
         outputs, or a first frame's own), seen through prev_view from prev_eye.  Without a
         history the outputs are copies.  Returns (out_rgba, out_mom) in rgba's and mom's
-        shapes; keep them with feat, ids and the camera as the next frame's history."""
+        shapes; keep them with feat, ids and the camera as the next frame's history.
+        With `motion`, the (n, 8) table of sphere_motion(scene, prev_scene), the history
+        follows the spheres that moved between the two frames (spt_temporal_motion)."""
         rgba, feat, w, h = self._denoise_inputs(rgba, feat)
         n = w * h
 
@@ -530,29 +532,40 @@ class Context:
             cam[2:] = [_view16(prev_view), _eye4(prev_eye)]
         out, out_mom = np.zeros_like(rgba), np.zeros_like(mom)
         ptr = lambda a: None if a is None else _p(a)  # noqa: E731
-        self._check(_native.lib().spt_temporal(self._h, w, h, _p(rgba), _p(mom), _p(feat), _p(ids), _p(cam[0]), _p(cam[1]),
-                                               ptr(hist[0]), ptr(hist[1]), ptr(hist[2]), ptr(hist[3]), ptr(cam[2]),
-                                               ptr(cam[3]), tol_normal, tol_depth, max_history, _p(out), _p(out_mom)))
+        args = [self._h, w, h, _p(rgba), _p(mom), _p(feat), _p(ids), _p(cam[0]), _p(cam[1]), ptr(hist[0]), ptr(hist[1]),
+                ptr(hist[2]), ptr(hist[3]), ptr(cam[2]), ptr(cam[3])]
+        if motion is None:
+            self._check(_native.lib().spt_temporal(*args, tol_normal, tol_depth, max_history, _p(out), _p(out_mom)))
+            return out, out_mom
+        motion = _motion_table(motion)
+        self._check(_native.lib().spt_temporal_motion(*args, _p(motion) if len(motion) else None, len(motion), tol_normal,
+                                                      tol_depth, max_history, _p(out), _p(out_mom)))
         return out, out_mom
 
     def temporal_async(self, width, height, d_rgba, d_mom, d_feat, d_ids, view, eye, d_hist=None, prev_view=None,
                        prev_eye=None, tol_normal=0.25, tol_depth=0.1, max_history=64.0, d_out_rgba=0, d_out_mom=0,
-                       stream=0) -> None:
+                       stream=0, d_motion=0, n_spheres=0) -> None:
         """Device-resident temporal (spt_temporal_async): raw device pointers to this frame's
         width * height float4 colours, float4 moments, 8 floats of features and uint32 ids per
         pixel, d_hist the tuple of the previous frame's four pointers (or None), and the two
         float4 outputs; the cameras are host arrays, read before the call returns.  One launch
-        on `stream` (a hipStream_t; 0 = the default stream)."""
+        on `stream` (a hipStream_t; 0 = the default stream).  With d_motion, a device pointer to
+        the n_spheres records of sphere_motion's table, spt_temporal_motion_async instead."""
         cam = [_view16(view), _eye4(eye), None if prev_view is None else _view16(prev_view),
                None if prev_eye is None else _eye4(prev_eye)]
         dh = tuple(d_hist) if d_hist is not None else (0, 0, 0, 0)
         ptr = lambda a: None if a is None else _p(a)  # noqa: E731
-        self._check(_native.lib().spt_temporal_async(
-            self._h, int(width), int(height), ctypes.c_void_p(d_rgba or None), ctypes.c_void_p(d_mom or None),
-            ctypes.c_void_p(d_feat or None), ctypes.c_void_p(d_ids or None), ptr(cam[0]), ptr(cam[1]),
-            ctypes.c_void_p(dh[0] or None), ctypes.c_void_p(dh[1] or None), ctypes.c_void_p(dh[2] or None),
-            ctypes.c_void_p(dh[3] or None), ptr(cam[2]), ptr(cam[3]), tol_normal, tol_depth, max_history,
-            ctypes.c_void_p(d_out_rgba or None), ctypes.c_void_p(d_out_mom or None), ctypes.c_void_p(stream or None)))
+        args = [self._h, int(width), int(height), ctypes.c_void_p(d_rgba or None), ctypes.c_void_p(d_mom or None),
+                ctypes.c_void_p(d_feat or None), ctypes.c_void_p(d_ids or None), ptr(cam[0]), ptr(cam[1]),
+                ctypes.c_void_p(dh[0] or None), ctypes.c_void_p(dh[1] or None), ctypes.c_void_p(dh[2] or None),
+                ctypes.c_void_p(dh[3] or None), ptr(cam[2]), ptr(cam[3])]
+        tail = [tol_normal, tol_depth, max_history, ctypes.c_void_p(d_out_rgba or None), ctypes.c_void_p(d_out_mom or None),
+                ctypes.c_void_p(stream or None)]
+        if not d_motion and not n_spheres:
+            self._check(_native.lib().spt_temporal_async(*args, *tail))
+        else:
+            self._check(_native.lib().spt_temporal_motion_async(*args, ctypes.c_void_p(d_motion or None), int(n_spheres),
+                                                                *tail))
 
     def render_denoised(self, variance=False, adaptive=None, **sigmas) -> np.ndarray:
         """The current frame rendered, its feature buffers, and the frame filtered by denoise
@@ -643,6 +656,26 @@ def _eye4(eye) -> np.ndarray:
     return np.ascontiguousarray(np.concatenate([e[:3], np.zeros(1, np.float32)]))
 
 
+def _motion_table(motion) -> np.ndarray:
+    """A motion table as the C ABI reads it: (n, 8) float32, contiguous."""
+    m = np.ascontiguousarray(motion, np.float32)
+    if m.size % 8:
+        raise ValueError(f"motion: expected 8 floats per sphere, got shape {m.shape}")
+    return m.reshape(-1, 8)
+
+
+def sphere_motion(scene: Scene, prev_scene: Scene) -> np.ndarray:
+    """The (n, 8) float32 motion table of Context.temporal(motion=...): per sphere {C.xyz, r}
+    of `scene`, this frame's, then {Cp.xyz, rp} of `prev_scene`, the previous frame's.  The
+    two scenes hold the same spheres in the same order; ValueError when their counts differ."""
+    if scene.n != prev_scene.n:
+        raise ValueError(f"sphere_motion: {scene.n} spheres now, {prev_scene.n} in the previous scene")
+    out = np.zeros((scene.n, 8), np.float32)
+    out[:, 0:3], out[:, 3] = scene.centers[:, :3], scene.radii
+    out[:, 4:7], out[:, 7] = prev_scene.centers[:, :3], prev_scene.radii
+    return out
+
+
 def temporal_inverse(view) -> np.ndarray:
     """The (3, 3) float32 inverse of view's upper-left 3x3 as Context.temporal uses it for the
     previous camera (spt_temporal_inverse): computed in double, rounded once per entry."""
@@ -653,39 +686,123 @@ def temporal_inverse(view) -> np.ndarray:
 
 
 class TemporalAccumulator:
-    """A preview that keeps its samples while the camera moves: every frame(view, eye) renders
-    width x height at spp samples with a seed of its own, accumulates it against the stored
-    history (Context.temporal, whose keyword arguments `temporal_kwargs` takes) and stores the
-    accumulated, unfiltered result as the next frame's history.  The context's scene must be
-    set; camera and params are set by every frame."""
+    """A preview that keeps its samples while the camera and the spheres move: every
+    frame(view, eye) renders width x height at spp samples with a seed of its own, accumulates
+    it against the stored history (Context.temporal, whose keyword arguments `temporal_kwargs`
+    takes) and stores the accumulated, unfiltered result as the next frame's history.  The
+    context's scene must be set, by the caller or by frame(scene=...); camera and params are
+    set by every frame.
 
-    def __init__(self, ctx: Context, width, height, spp, bounces, seed=1, sky=INIT_COLOR, **temporal_kwargs):
+    With resident=True the frame's colour, moments, features and ids and the history (a
+    ping-pong pair) live in torch tensors on the context's device, and a frame is the
+    device-pointer forms enqueued on one stream of the accumulator's own, then one copy of the
+    returned image to the host: the history never crosses the host link.  The images are the
+    non-resident accumulator's, bit for bit."""
+
+    def __init__(self, ctx: Context, width, height, spp, bounces, seed=1, sky=INIT_COLOR, resident=False,
+                 **temporal_kwargs):
         self.ctx, self.width, self.height, self.spp, self.bounces = ctx, int(width), int(height), int(spp), int(bounces)
         self.seed, self.sky, self.kwargs = int(seed), sky, temporal_kwargs
+        self.resident = bool(resident)
+        self._dev = None  # the resident tensors, made by the first resident frame
         self.reset()
 
     def reset(self) -> None:
         """Forget the history and start the seeds again: the next frame passes through."""
         self.frame_index = 0
-        self._history = None  # ((rgba, mom, feat, ids), view, eye)
+        self._history = None  # ((rgba, mom, feat, ids), view, eye); resident: (slot, view, eye)
+        self._spheres = None  # (n, 4): {C.xyz, r} of the last frame(scene=...)'s scene
 
-    def frame(self, view, eye, denoise=None) -> np.ndarray:
+    def _set_scene(self, scene):
+        """set_scene for frame(scene=...); returns the motion table against the previous
+        frame's scene, or None where there is none to follow."""
+        now = np.concatenate([scene.centers[:, :3], scene.radii[:, None]], axis=1).astype(np.float32)
+        motion = None
+        if self._spheres is not None:
+            if len(now) != len(self._spheres):
+                raise ValueError(f"frame: {len(now)} spheres now, {len(self._spheres)} in the previous frame's scene")
+            if self._history is not None:
+                motion = np.ascontiguousarray(np.concatenate([now, self._spheres], axis=1))
+        self.ctx.set_scene(scene)
+        self._spheres = now
+        return motion
+
+    def frame(self, view, eye, denoise=None, scene=None) -> np.ndarray:
         """The accumulated (H, W, 4) image of the next frame seen through `view` from `eye`;
         with denoise=dict(...) (denoise_variance's keyword arguments, {} for its defaults)
         that filter's result on the accumulated colour and moments instead.  The history
-        kept is the unfiltered one either way."""
+        kept is the unfiltered one either way.  With scene=..., that scene is set first
+        (Context.set_scene) and the history follows its spheres from where the previous
+        frame's scene had them (sphere_motion; the same spheres in the same order: ValueError
+        when the counts differ); the first scene given has none to follow."""
         c, w, h = self.ctx, self.width, self.height
+        motion = self._set_scene(scene) if scene is not None else None
         c.set_camera(view, _eye4(eye), self.sky)
         c.set_params(w, h, self.spp, self.bounces, self.seed + self.frame_index)
+        kw = dict(self.kwargs) if motion is None else dict(self.kwargs, motion=motion)
+        if self.resident:
+            return self._resident_frame(view, eye, denoise, kw)
         rgba, mom = c.render_moments(0, h, 0, w)
         feat, ids = c.render_features(0, h, 0, w, ids=True)
         hist, pv, pe = self._history if self._history is not None else (None, None, None)
-        out, out_mom = c.temporal(rgba.reshape(h, w, 4), mom, feat, ids, view, eye, hist, pv, pe, **self.kwargs)
+        out, out_mom = c.temporal(rgba.reshape(h, w, 4), mom, feat, ids, view, eye, hist, pv, pe, **kw)
         self._history = ((out, out_mom, feat, ids), _view16(view).copy(), _eye4(eye))
         self.frame_index += 1
         if denoise is not None:
             return c.denoise_variance(out, feat, out_mom, **denoise)
         return out
+
+    def _resident_frame(self, view, eye, denoise, kw):
+        import torch
+        c, w, h, n = self.ctx, self.width, self.height, self.width * self.height
+        if self._dev is None:
+            dev = torch.device("cuda", c.device)
+            f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)  # noqa: E731
+            slot = lambda: dict(rgba=f32(n, 4), mom=f32(n, 4), feat=f32(n, 8),  # noqa: E731
+                                ids=torch.zeros(n, dtype=torch.int32, device=dev))
+            self._dev = dict(device=dev, stream=torch.cuda.Stream(device=dev), raw_rgba=f32(n, 4), raw_mom=f32(n, 4),
+                             slots=(slot(), slot()), filtered=None, scratch=None, table=None)
+            torch.cuda.synchronize(dev)  # the tensors are zeroed before the stream below writes them
+        d = self._dev
+        stream, s = d["stream"], d["stream"].cuda_stream
+        cur = d["slots"][self.frame_index & 1]
+        c.synchronize()  # the scene, camera and params are in place
+        c.render_moments_async(0, h, 1, 1, 0, 0, w, d_rgba=d["raw_rgba"].data_ptr(), d_mom=d["raw_mom"].data_ptr(), stream=s)
+        c.render_features_async(0, h, 1, 1, 0, 0, w, cur["feat"].data_ptr(), cur["ids"].data_ptr(), s)
+        d_hist = pv = pe = None
+        if self._history is not None:
+            prev, pv, pe = self._history
+            d_hist = tuple(prev[k].data_ptr() for k in ("rgba", "mom", "feat", "ids"))
+        motion = kw.pop("motion", None)
+        if motion is not None:
+            if d["table"] is None or d["table"].numel() != motion.size:
+                d["table"] = torch.zeros(motion.size, dtype=torch.float32, device=d["device"])
+                torch.cuda.synchronize(d["device"])
+            with torch.cuda.stream(stream):
+                d["table"].copy_(torch.from_numpy(motion.reshape(-1)), non_blocking=True)
+            kw.update(d_motion=d["table"].data_ptr(), n_spheres=len(motion))
+        c.temporal_async(w, h, d["raw_rgba"].data_ptr(), d["raw_mom"].data_ptr(), cur["feat"].data_ptr(),
+                         cur["ids"].data_ptr(), view, eye, d_hist, pv, pe, d_out_rgba=cur["rgba"].data_ptr(),
+                         d_out_mom=cur["mom"].data_ptr(), stream=s, **kw)
+        result = cur["rgba"]
+        if denoise is not None:
+            if "g_data" in denoise or "variance" in denoise:
+                raise ValueError("a resident frame returns the filtered image alone: no g_data or variance")
+            levels = int(denoise.get("levels", 3))
+            need = denoise_scratch_bytes(w, h, levels)
+            if d["filtered"] is None or d["scratch"].numel() < need:
+                d["filtered"] = torch.zeros((n, 4), dtype=torch.float32, device=d["device"])
+                d["scratch"] = torch.zeros(max(need, 16), dtype=torch.uint8, device=d["device"])
+                torch.cuda.synchronize(d["device"])
+            c.denoise_variance_async(w, h, cur["rgba"].data_ptr(), cur["feat"].data_ptr(), cur["mom"].data_ptr(),
+                                     d_out=d["filtered"].data_ptr(), d_scratch=d["scratch"].data_ptr(), stream=s, **denoise)
+            result = d["filtered"]
+        with torch.cuda.stream(stream):
+            host = result.to("cpu")  # the one copy of the frame that crosses the host link
+        stream.synchronize()
+        self._history = (cur, _view16(view).copy(), _eye4(eye))
+        self.frame_index += 1
+        return host.numpy().reshape(h, w, 4)
 
 
 class Globals:
