@@ -114,7 +114,7 @@ typedef struct spt_stats {
     uint64_t svc_closing_restarts; /* sessions ended because a wave had raised its closing flag */
     uint32_t prim_list_blocks;   /* 8x8 pixel blocks with a primary-ray candidate list (0: lists off) */
     uint32_t prim_list_entries;  /* candidate slots over all blocks' lists (8x8 and 8x4) */
-    double prim_list_build_ms;   /* host time of their last build */
+    double prim_list_build_ms;   /* host time of their last build (device time where spt_update_scene built them) */
     uint64_t prim_list_builds;   /* builds so far (a setter rebuilds the lists only when the
                                     accel tables, the camera or the frame size changed) */
     double accel_build_ms;       /* host time of the last traversal-table build + upload
@@ -225,6 +225,62 @@ SPT_API int spt_prim_lists_check(const float *centers4, const float *radii, uint
                                  const float eye[4], uint32_t width, uint32_t height, uint32_t max_count,
                                  uint32_t *blocks8, uint32_t *blocks4, uint32_t *slot_ids, uint32_t *slot_orig,
                                  uint32_t cap, uint32_t *counts);
+
+/* ---- scene updates ------------------------------------------------------
+ * An animation frame moves spheres and the camera by a little.  spt_update_scene applies the
+ * new centres and / or the new camera without the setters' host work: the traversal tables
+ * are refit -- their shape (slot order, leaves, tree topology, sibling order) stays, every
+ * bound and pretest constant is recomputed with the builder's arithmetic -- and the
+ * primary-ray candidate lists are built by a kernel on the device. */
+typedef struct spt_update_info {
+    double refit_ms;           /* host: refit + upload (0 when no centres were given) */
+    double lists_ms;           /* device time of the list build (events), 0 if none */
+    uint32_t list_blocks, list_entries;  /* as spt_stats' prim_list_blocks / prim_list_entries */
+    uint32_t lists_on_device;  /* 1: built by the kernel; 0: the host builder was used, or lists are off */
+    uint32_t refit;            /* 1: centres were applied */
+    /* why lists_on_device is 0 (SPT_UPDATE_LISTS_*; 0 when it is 1) */
+    uint32_t lists_reason;
+} spt_update_info;
+#define SPT_UPDATE_LISTS_DEVICE 0u     /* built on the device */
+#define SPT_UPDATE_LISTS_OFF 1u        /* no lists for this state: camera or params not set, a tree walked
+                                          lane by lane, SPT_PRIM_LISTS=0 */
+#define SPT_UPDATE_LISTS_CAMERA 2u     /* host builder's call: non-finite camera or a frame beyond 65 535 */
+#define SPT_UPDATE_LISTS_SLOTS 3u      /* more slots than the kernel's list holds (2 048, or
+                                          SPT_PRIM_DEVICE_SLOTS if lower): host builder */
+#define SPT_UPDATE_LISTS_UNCHANGED 4u  /* nothing the lists depend on changed: kept */
+/* centers4 (nullable: the spheres stay): n float4 in the order of spt_set_scene (w ignored);
+ * radii, colours, materials and fuzz are unchanged.  view / eye (nullable together: the camera
+ * stays; the sky stays either way) as spt_set_camera.  Needs a scene (SPT_ERR_STATE before
+ * spt_set_scene); the lists are built once camera and params are set.  A centre that is not
+ * finite is SPT_ERR_ARG with the context unchanged (build puts such spheres in the always-
+ * list, which a refit cannot); finite centres of any size are accepted.  Afterwards every
+ * entry point behaves, bit for bit, as after spt_set_scene with the moved centres and
+ * spt_set_camera with the new camera; only the culling (the tree's shape is the old scene's)
+ * and so the speed may differ.  Like the setters: not from a progress callback, ends a
+ * render-service session, applies to every member of a multi-device context (info: member
+ * 0's), waits for the device before it writes a table. */
+SPT_API int spt_update_scene(spt_ctx *ctx, const float *centers4, const float view[16], const float eye[4],
+                             spt_update_info *info /* nullable */);
+/* Host-only check (no device needed): build the traversal tables for (centers_a, radii) as
+ * spt_accel_check does; with refit != 0 refit them to centers_b (spt_update_scene's refit)
+ * and verify the result against centers_b as spt_accel_check verifies a build, with refit
+ * == 0 return the build for centers_a itself (centers_b unused).  counts[4] = {slots, node
+ * records of all 8 layouts (pads included), nodes per layout, leaves}.  The tables, each
+ * nullable: slots4 (4 floats per slot), orig and kpre (one word per slot), nodes (8 words
+ * per record: the 32-byte record as stored) of capacities cap_slots slots / cap_nodes
+ * records; *pre_cm the scene bound of the member pretest. */
+SPT_API int spt_accel_refit_check(const float *centers_a, const float *centers_b, const float *radii, uint32_t n,
+                                  uint32_t cluster_k, uint32_t branching, int refit, uint32_t *counts, float *slots4,
+                                  uint32_t *orig, float *kpre, uint32_t *nodes, float *pre_cm, uint32_t cap_slots,
+                                  uint32_t cap_nodes);
+/* The context's candidate lists in spt_prim_lists_check's output format: which = 0 the lists
+ * its device holds now (read back; runs are at fixed strides when the device built them,
+ * packed when the host did), which = 1 the host builder's lists for the context's current
+ * tables, camera and frame (built now, on the host; the context's own lists stay).  counts[3]
+ * = 0: lists off.  Member 0 of a multi-device context. */
+SPT_API int spt_prim_lists_read(spt_ctx *ctx, int which, uint32_t *blocks8, uint32_t *blocks4, uint32_t *slot_ids,
+                                uint32_t *slot_orig, uint32_t cap, uint32_t *counts);
+
 /* Engine of the render loop (results are bit-identical either way):
  * SPT_ENGINE_MEGAKERNEL (default) -- one persistent kernel, per-lane state machines;
  * SPT_ENGINE_WAVEFRONT -- RenderSegmentTask's material-queue design

@@ -64,6 +64,23 @@ class Stats(ctypes.Structure):
     ]
 
 
+class UpdateInfo(ctypes.Structure):
+    """spt_update_info (include/spt_hip.h "scene updates")."""
+    _fields_ = [
+        ("refit_ms", ctypes.c_double),
+        ("lists_ms", ctypes.c_double),
+        ("list_blocks", ctypes.c_uint32),
+        ("list_entries", ctypes.c_uint32),
+        ("lists_on_device", ctypes.c_uint32),
+        ("refit", ctypes.c_uint32),
+        ("lists_reason", ctypes.c_uint32),
+    ]
+
+
+# spt_update_info.lists_reason (SPT_UPDATE_LISTS_*)
+UPDATE_LISTS_REASONS = {0: "device", 1: "off", 2: "camera", 3: "slots", 4: "unchanged"}
+
+
 def build(force: bool = False) -> str:
     """Compile the gfx950 library in-tree (hipcc via the csrc Makefile)."""
     if force or not os.path.exists(LIB_PATH):
@@ -111,6 +128,9 @@ def lib() -> ctypes.CDLL:
         "spt_set_engine": ([P, I], I),
         "spt_accel_check": ([P, P, u32, u32, u32, P], I),
         "spt_prim_lists_check": ([P, P, u32, P, P, u32, u32, u32, P, P, P, P, u32, P], I),
+        "spt_update_scene": ([P, P, P, P, P], I),
+        "spt_accel_refit_check": ([P, P, P, u32, u32, u32, I, P, P, P, P, P, P, u32, u32], I),
+        "spt_prim_lists_read": ([P, I, P, P, P, P, u32, P], I),
         "spt_render_segment": ([P, u32, u32, u32, u32, P, P], I),
         "spt_render_segment_task": ([P, u32, u32, u32, u32, P, P], I),
         "spt_render_rows_async": ([P, I, u32, u32, u32, u32, u32, u32, u32, P, P, P], I),

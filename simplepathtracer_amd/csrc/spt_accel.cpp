@@ -35,6 +35,7 @@
 // octant, differ only in sibling order.
 #include "spt_accel.h"
 #include "spt_internal.h"
+#include "spt_primcone.h"  // prim_cone, prim_candidate: shared with the device builder
 
 #pragma clang fp contract(off)
 
@@ -105,22 +106,39 @@ double node_reach(const float *centers4, const float *radii, const uint32_t *idx
 // Tree node box of the members idx[0..m): lo = min (C - |r|) - kBoxS Bm
 // rounded down, hi = max (C + |r|) + kBoxS Bm rounded up.  Members beyond 1e15 from the
 // origin: the box is everything (the node never culls).
-AccelNode box_node(const float *centers4, const float *radii, const uint32_t *idx, size_t m)
-{
-    AccelNode nd{};
-    const double bm = node_reach(centers4, radii, idx, m);
+// The extent in double comes first (BoxExtent: min, max and Bm are exact and order-free, so
+// the extent of a subtree is the merge of its children's, which is how refit_accel gets an
+// inner node's without gathering its members); box_of rounds it into the record.
+struct BoxExtent {
     double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (size_t j = 0; j < m; ++j)
+    double bm = 0;
+    void add(const float *centers4, const float *radii, uint32_t i)
+    {
+        bm = std::max(bm, member_reach(centers4, radii, i));
         for (int c = 0; c < 3; ++c) {
-            const double cc = centers4[4 * idx[j] + c], r = std::fabs((double)radii[idx[j]]);
+            const double cc = centers4[4 * i + c], r = std::fabs((double)radii[i]);
             lo[c] = std::min(lo[c], cc - r);
             hi[c] = std::max(hi[c], cc + r);
         }
+    }
+    void merge(const BoxExtent &o)
+    {
+        bm = std::max(bm, o.bm);
+        for (int c = 0; c < 3; ++c) {
+            lo[c] = std::min(lo[c], o.lo[c]);
+            hi[c] = std::max(hi[c], o.hi[c]);
+        }
+    }
+};
+
+// the six box words of a tree node record (skip and slot are left alone)
+void box_of(const BoxExtent &e, AccelNode &nd)
+{
     float flo[3], fhi[3];
     for (int c = 0; c < 3; ++c) {
-        const bool off = !(bm <= 1e15);
-        flo[c] = off ? -INFINITY : round_down(lo[c] - kBoxS * bm);
-        fhi[c] = off ? INFINITY : round_up(hi[c] + kBoxS * bm);
+        const bool off = !(e.bm <= 1e15);
+        flo[c] = off ? -INFINITY : round_down(e.lo[c] - kBoxS * e.bm);
+        fhi[c] = off ? INFINITY : round_up(e.hi[c] + kBoxS * e.bm);
     }
     nd.lox = flo[0];
     nd.loy = flo[1];
@@ -128,7 +146,92 @@ AccelNode box_node(const float *centers4, const float *radii, const uint32_t *id
     nd.hix = fhi[0];
     nd.hiy = fhi[1];
     nd.hiz = fhi[2];
+}
+
+AccelNode box_node(const float *centers4, const float *radii, const uint32_t *idx, size_t m)
+{
+    AccelNode nd{};
+    BoxExtent e;
+    for (size_t j = 0; j < m; ++j) e.add(centers4, radii, idx[j]);
+    box_of(e, nd);
     return nd;
+}
+
+// centre of the members' centres (the bounding sphere's Cb, and the key of the sibling order)
+void centre_of(const float *centers4, const uint32_t *idx, size_t m, double ctr[3])
+{
+    double clo[3] = {INFINITY, INFINITY, INFINITY}, chi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (size_t j = 0; j < m; ++j)
+        for (int c = 0; c < 3; ++c) {
+            clo[c] = std::min(clo[c], (double)centers4[4 * idx[j] + c]);
+            chi[c] = std::max(chi[c], (double)centers4[4 * idx[j] + c]);
+        }
+    for (int c = 0; c < 3; ++c) ctr[c] = (clo[c] + chi[c]) / 2;
+}
+
+// The bounding-sphere words of a flat-list node record over the members idx[0..m) (skip and
+// slot are left alone): Cb, K1, K1'' and c |Cb|^2.
+void flat_bound(const float *centers4, const float *radii, const uint32_t *idx, size_t m, AccelNode &nd)
+{
+    double ctr[3];
+    centre_of(centers4, idx, m, ctr);
+    const float cbf[3] = {(float)ctr[0], (float)ctr[1], (float)ctr[2]};
+    double rb = 0;
+    for (size_t j = 0; j < m; ++j) {
+        const uint32_t i = idx[j];
+        double d2 = 0;
+        for (int c = 0; c < 3; ++c) {
+            const double dd = (double)centers4[4 * i + c] - (double)cbf[c];
+            d2 += dd * dd;
+        }
+        rb = std::max(rb, std::sqrt(d2) + std::fabs((double)radii[i]));
+    }
+    rb *= 1.0 + 1e-6;
+    nd.cx = cbf[0];
+    nd.cy = cbf[1];
+    nd.cz = cbf[2];
+    const float rbf = round_up(rb);
+    nd.k1 = round_up(1.15 * (double)rbf * (double)rbf + 1e-5);
+    // expanded line test (spt_path.h find_closest): K1'' = K1 +
+    // 4e-6 |Cb|^2 - c |Cb|^2 -- the kernel leaves c |Cb|^2 out of the per-lane sum
+    // and compares against K1'' instead (one add fewer)
+    const double cbb = (double)nd.cx * nd.cx + (double)nd.cy * nd.cy + (double)nd.cz * nd.cz;
+    nd.cb2 = (float)(kFlatScale * cbb);
+    nd.rb = round_up((double)nd.k1 + 4e-6 * cbb - (double)nd.cb2);
+    if (!(std::sqrt(cbb) + rb <= 1e15)) {
+        // squares near the float range (K1, c |Cb|^2 overflow and K1'' = inf - inf):
+        // the node never culls, like the tree boxes and the member pretest past 1e15
+        nd.cx = nd.cy = nd.cz = 0.f;
+        nd.cb2 = 0.f;
+        nd.k1 = nd.rb = INFINITY;
+    }
+}
+
+// Member pretest constants of the cluster slots [cbase, end) and the scene bound pre_cm
+// (dummies: K' = +inf never passes; the always-list keeps 0)
+void fill_pretest(AccelTables &t, size_t cbase, const float *centers4, const float *radii)
+{
+    t.kpre.assign(t.slots.size(), 0.f);
+    double cm = 0;
+    for (size_t j = cbase; j < t.slots.size(); ++j) {
+        if (t.orig[j] == 0xFFFFFFFFu) {
+            t.kpre[j] = INFINITY;
+            continue;
+        }
+        const float4 &q = t.slots[j];
+        t.kpre[j] = pretest_k(q);
+        // over the slot's r*r (the pretest) and the sphere's |r| (tree boxes' Bm)
+        cm = std::max({cm,
+                       std::sqrt((double)q.x * q.x + (double)q.y * q.y + (double)q.z * q.z) + std::sqrt((double)q.w),
+                       member_reach(centers4, radii, t.orig[j])});
+    }
+    t.pre_cm = round_up(cm * (1.0 + 1e-9));
+    if (!(cm <= 1e15)) {
+        // squares near the float range: the pretest passes every lane (K' = -inf)
+        t.pre_cm = INFINITY;
+        for (size_t j = cbase; j < t.slots.size(); ++j)
+            if (t.orig[j] != 0xFFFFFFFFu) t.kpre[j] = -INFINITY;
+    }
 }
 
 // the record one past a layout's last node (the kernels prefetch it; never tested)
@@ -321,47 +424,11 @@ AccelTables build_accel(const float *centers4, const float *radii, uint32_t n, u
         // leaves [c0, c1); `ctr` = centre of the members' centres (sibling order)
         auto bound = [&](const TNode &sp, AccelNode &nd, double *ctr) {
             const size_t j0 = (size_t)sp.c0 * k, j1 = sph_end(sp.c1);
-            double clo[3] = {INFINITY, INFINITY, INFINITY}, chi[3] = {-INFINITY, -INFINITY, -INFINITY};
-            for (size_t j = j0; j < j1; ++j)
-                for (int c = 0; c < 3; ++c) {
-                    clo[c] = std::min(clo[c], (double)centers4[4 * sorted[j] + c]);
-                    chi[c] = std::max(chi[c], (double)centers4[4 * sorted[j] + c]);
-                }
-            for (int c = 0; c < 3; ++c) ctr[c] = (clo[c] + chi[c]) / 2;
-            if (tree) {
+            centre_of(centers4, sorted.data() + j0, j1 - j0, ctr);
+            if (tree)
                 nd = box_node(centers4, radii, sorted.data() + j0, j1 - j0);
-                return;
-            }
-            const float cbf[3] = {(float)ctr[0], (float)ctr[1], (float)ctr[2]};
-            double rb = 0;
-            for (size_t j = j0; j < j1; ++j) {
-                const uint32_t i = sorted[j];
-                double d2 = 0;
-                for (int c = 0; c < 3; ++c) {
-                    const double dd = (double)centers4[4 * i + c] - (double)cbf[c];
-                    d2 += dd * dd;
-                }
-                rb = std::max(rb, std::sqrt(d2) + std::fabs((double)radii[i]));
-            }
-            rb *= 1.0 + 1e-6;
-            nd.cx = cbf[0];
-            nd.cy = cbf[1];
-            nd.cz = cbf[2];
-            const float rbf = round_up(rb);
-            nd.k1 = round_up(1.15 * (double)rbf * (double)rbf + 1e-5);
-            // expanded line test (spt_path.h find_closest): K1'' = K1 +
-            // 4e-6 |Cb|^2 - c |Cb|^2 -- the kernel leaves c |Cb|^2 out of the per-lane sum
-            // and compares against K1'' instead (one add fewer)
-            const double cbb = (double)nd.cx * nd.cx + (double)nd.cy * nd.cy + (double)nd.cz * nd.cz;
-            nd.cb2 = (float)(kFlatScale * cbb);
-            nd.rb = round_up((double)nd.k1 + 4e-6 * cbb - (double)nd.cb2);
-            if (!(std::sqrt(cbb) + rb <= 1e15)) {
-                // squares near the float range (K1, c |Cb|^2 overflow and K1'' = inf - inf):
-                // the node never culls, like the tree boxes and the member pretest past 1e15
-                nd.cx = nd.cy = nd.cz = 0.f;
-                nd.cb2 = 0.f;
-                nd.k1 = nd.rb = INFINITY;
-            }
+            else
+                flat_bound(centers4, radii, sorted.data() + j0, j1 - j0, nd);
         };
         // Preorder emission, once per direction octant: siblings are ordered front to
         // back along the octant's diagonal, so a wave walking the layout of its
@@ -406,29 +473,76 @@ AccelTables build_accel(const float *centers4, const float *radii, uint32_t n, u
     }
     if (t.nodes.empty())  // no tree: one pad record per octant layout (n_nodes = 0)
         for (int oct = 0; oct < 8; ++oct) t.nodes.push_back(pad_node(1));
-    // member pretest constants of the cluster slots (dummies: K' = +inf never passes)
-    t.kpre.assign(t.slots.size(), 0.f);
-    double cm = 0;
-    for (size_t j = cbase; j < t.slots.size(); ++j) {
-        if (t.orig[j] == 0xFFFFFFFFu) {
-            t.kpre[j] = INFINITY;
-            continue;
-        }
-        const float4 &q = t.slots[j];
-        t.kpre[j] = pretest_k(q);
-        // over the slot's r*r (the pretest) and the sphere's |r| (tree boxes' Bm)
-        cm = std::max({cm,
-                       std::sqrt((double)q.x * q.x + (double)q.y * q.y + (double)q.z * q.z) + std::sqrt((double)q.w),
-                       member_reach(centers4, radii, t.orig[j])});
-    }
-    t.pre_cm = round_up(cm * (1.0 + 1e-9));
-    if (!(cm <= 1e15)) {
-        // squares near the float range: the pretest passes every lane (K' = -inf)
-        t.pre_cm = INFINITY;
-        for (size_t j = cbase; j < t.slots.size(); ++j)
-            if (t.orig[j] != 0xFFFFFFFFu) t.kpre[j] = -INFINITY;
-    }
+    fill_pretest(t, cbase, centers4, radii);
     return t;
+}
+
+// Refit: the tables of the same spheres at new centres, with the shape
+// build_accel gave them.  Slot order, orig, the always / cluster split, leaf membership, the
+// preorder with its skip links and the sibling order of the eight layouts stay; slot centres,
+// the pretest constants and every node's bound are recomputed with build_accel's own
+// arithmetic (box_of, flat_bound, fill_pretest), so the result is what build_accel emits for
+// this shape at these centres.  The cull conditions use only the containment of a node's
+// members, which the new bounds restore; a stale shape costs culling, never exactness.
+std::string refit_accel(AccelTables &t, const float *centers4, const float *radii, uint32_t n)
+{
+    // build_accel puts spheres with non-finite centres in the always-list: a refit cannot
+    // move a slot there
+    for (uint32_t i = 0; i < n; ++i)
+        for (int c = 0; c < 3; ++c)
+            if (!std::isfinite(centers4[4 * i + c])) {
+                char buf[96];
+                std::snprintf(buf, sizeof buf, "sphere %u: centre not finite (a refit keeps the table's shape)", i);
+                return std::string(buf);
+            }
+    const size_t cbase = (size_t)t.always_groups * t.group;
+    if (t.slots.size() != t.orig.size() || t.nodes.size() != 8 * ((size_t)t.n_nodes + 1) || cbase > t.slots.size())
+        return std::string("refit of tables that no build made");
+    for (size_t j = 0; j < t.slots.size(); ++j)
+        if (t.orig[j] != 0xFFFFFFFFu && t.orig[j] >= n) return std::string("refit with fewer spheres than the tables hold");
+    for (size_t j = 0; j < t.slots.size(); ++j) {
+        const uint32_t o = t.orig[j];
+        if (o == 0xFFFFFFFFu) continue;
+        t.slots[j].x = centers4[4 * o];
+        t.slots[j].y = centers4[4 * o + 1];
+        t.slots[j].z = centers4[4 * o + 2];
+    }
+    if (t.n_nodes > 0) {
+        const bool tree = t.n_nodes > t.leaves;
+        // per leaf (in slot order): its members, and for trees their extent
+        uint32_t idx[kClusterSlots];
+        auto members = [&](uint32_t slot) {
+            size_t m = 0;
+            for (uint32_t q = 0; q < t.leaf_slots; ++q)
+                if (t.orig[slot + q] != 0xFFFFFFFFu) idx[m++] = t.orig[slot + q];
+            return m;
+        };
+        std::vector<BoxExtent> leaf(tree ? t.leaves : 0), sub(tree ? t.n_nodes : 0);
+        for (size_t c = 0; c < leaf.size(); ++c) {
+            const size_t m = members((uint32_t)(cbase + c * t.leaf_slots));
+            for (size_t j = 0; j < m; ++j) leaf[c].add(centers4, radii, idx[j]);
+        }
+        for (uint32_t oct = 0; oct < 8; ++oct) {
+            AccelNode *L = t.nodes.data() + (size_t)oct * (t.n_nodes + 1);
+            if (!tree) {
+                for (uint32_t i = 0; i < t.n_nodes; ++i) flat_bound(centers4, radii, idx, members(L[i].slot), L[i]);
+                continue;
+            }
+            // bottom up: in preorder every child has a larger index than its parent, and the
+            // children of node i are i + 1, skip[i + 1], ... up to skip[i]
+            for (uint32_t i = t.n_nodes; i-- > 0;) {
+                if (L[i].slot != kNoSlot) {
+                    sub[i] = leaf[(L[i].slot - cbase) / t.leaf_slots];
+                } else {
+                    sub[i] = BoxExtent{};
+                    for (uint32_t q = i + 1; q < L[i].skip; q = L[q].skip) sub[i].merge(sub[q]);
+                }
+                box_of(sub[i], L[i]);
+            }
+        }
+    }
+    fill_pretest(t, cbase, centers4, radii);
+    return std::string();
 }
 
 std::string validate_accel(const AccelTables &t, const float *centers4, const float *radii, uint32_t n)
@@ -571,88 +685,20 @@ std::string validate_accel(const AccelTables &t, const float *centers4, const fl
 // is the reference's winner over all spheres.  tests/test_abi.py checks every winner of
 // 4 096 sampled primary rays per scene against the lists (oracle rays, CPU);
 // tests/test_gpu_parity.py renders with and without the lists, bit for bit.
-namespace {
-
-struct PrimCone {
-    double a[3];
-    double theta, delta;
-    bool ok;
-};
-
-constexpr double kU = 1.0 / 16777216.0;  // 2^-24
-
-double norm3(const double v[3]) { return std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); }
-
-// angle between unit a and v (any length), robust near 0 and pi
-double angle_to(const double a[3], const double v[3])
+bool prim_camera_usable(const Camera &cam)
 {
-    const double cx = a[1] * v[2] - a[2] * v[1], cy = a[2] * v[0] - a[0] * v[2], cz = a[0] * v[1] - a[1] * v[0];
-    const double s = std::sqrt(cx * cx + cy * cy + cz * cz), c = a[0] * v[0] + a[1] * v[1] + a[2] * v[2];
-    return std::atan2(s, c);
+    bool finite = true;
+    for (int i = 0; i < 12; ++i) finite = finite && std::isfinite(cam.view[i]);
+    for (int i = 0; i < 3; ++i) finite = finite && std::isfinite(cam.eye[i]) && std::fabs(cam.eye[i]) < 1e15;
+    return finite;
 }
 
-// Cone of the primary rays of pixel columns [x0, x1), rows [y0, y1).
-PrimCone prim_cone(const Camera &cam, uint32_t W, uint32_t H, uint32_t x0, uint32_t x1, uint32_t y0, uint32_t y1)
+uint32_t prim_pad_slot(const AccelTables &t)
 {
-    PrimCone pc{};
-    // jittered row / column coordinates un = y + U, vn = x + U' (U in [-1, 1)), widened by
-    // their fp rounding, then u = un / W, v = vn / H (correctly rounded), vy = -1 + 2u,
-    // vx = -1 + 2v, each widened by its rounding
-    auto widen = [](double lo, double hi, double rel, double abs_) {
-        const double m = std::max(std::fabs(lo), std::fabs(hi));
-        return std::pair<double, double>(lo - m * rel - abs_, hi + m * rel + abs_);
-    };
-    auto un = widen((double)y0 - 1.0, (double)y1, 4 * kU, 1e-6);
-    auto vn = widen((double)x0 - 1.0, (double)x1, 4 * kU, 1e-6);
-    auto u = widen(un.first / (double)W, un.second / (double)W, 4 * kU, 1e-12);
-    auto v = widen(vn.first / (double)H, vn.second / (double)H, 4 * kU, 1e-12);
-    auto vy = widen(-1.0 + 2.0 * u.first, -1.0 + 2.0 * u.second, 4 * kU, 1e-7);
-    auto vx = widen(-1.0 + 2.0 * v.first, -1.0 + 2.0 * v.second, 4 * kU, 1e-7);
-    const float *m = cam.view;
-    auto dir = [&](double px, double py, double out[3], double &mag) {
-        mag = 0;
-        for (int r = 0; r < 3; ++r) {
-            const double t0 = (double)m[4 * r] * px, t1 = (double)m[4 * r + 1] * py, t2 = (double)m[4 * r + 2];
-            out[r] = t0 + t1 + t2;
-            mag += std::fabs(t0) + std::fabs(t1) + std::fabs(t2);
-        }
-    };
-    double c[3], cm;
-    dir(0.5 * (vx.first + vx.second), 0.5 * (vy.first + vy.second), c, cm);
-    const double cl = norm3(c);
-    if (!(cl > 0) || !std::isfinite(cl)) return pc;
-    for (int k = 0; k < 3; ++k) pc.a[k] = c[k] / cl;
-    double theta = 0, smax = cm, amin = 1e300;
-    for (int k = 0; k < 4; ++k) {
-        double d[3], dm;
-        dir(k & 1 ? vx.second : vx.first, k & 2 ? vy.second : vy.first, d, dm);
-        const double along = pc.a[0] * d[0] + pc.a[1] * d[1] + pc.a[2] * d[2];
-        if (!(along > 0) || !std::isfinite(along)) return pc;
-        theta = std::max(theta, angle_to(pc.a, d));
-        smax = std::max(smax, dm);
-        amin = std::min(amin, along);
-    }
-    if (!(theta < 0.5)) return pc;
-    pc.theta = theta;
-    pc.delta = 8 * kU * smax / amin + 6 * kU + 1e-6;
-    pc.ok = std::isfinite(pc.delta) && pc.delta < 1e-3;
-    return pc;
+    for (size_t s = t.slots.size(); s-- > 0;)
+        if (t.slots[s].w == -INFINITY) return (uint32_t)s;
+    return kPrimWalk;
 }
-
-// Can a primary ray of cone pc pass the member test of slot s (eye e)?
-bool prim_candidate(const PrimCone &pc, const float4 &sl, const double e[3])
-{
-    if (sl.w == -INFINITY) return false;  // dummy slot: never passes
-    const double c[3] = {(double)sl.x - e[0], (double)sl.y - e[1], (double)sl.z - e[2]};
-    const double L = norm3(c), r2 = (double)sl.w;
-    if (!std::isfinite(L) || !std::isfinite(r2)) return true;
-    const double R = std::sqrt(std::max(r2 + 2.6e-6 * L * L, 0.0)) * 1.001 + 1e-4;
-    if (!(L > R * 1.01 + 1e-3)) return true;
-    const double alpha = std::asin(std::min(1.0, R / L));
-    return angle_to(pc.a, c) <= pc.theta + alpha + pc.delta + 1e-6;
-}
-
-}  // namespace
 
 PrimListTables build_prim_lists(const AccelTables &t, const Camera &cam, uint32_t W, uint32_t H, uint32_t max_count)
 {
@@ -665,24 +711,12 @@ PrimListTables build_prim_lists(const AccelTables &t, const Camera &cam, uint32_
     const uint32_t bh8 = (H + 7) / 8, bh4 = (H + 3) / 4;
     out.b8.assign((size_t)out.bw * bh8, make_uint2(0, kPrimWalk));
     out.b4.assign((size_t)out.bw * bh4, make_uint2(0, kPrimWalk));
-    bool finite = true;
-    for (int i = 0; i < 12; ++i) finite = finite && std::isfinite(cam.view[i]);
-    double e[3];
-    for (int i = 0; i < 3; ++i) {
-        e[i] = cam.eye[i];
-        finite = finite && std::isfinite(cam.eye[i]) && std::fabs(cam.eye[i]) < 1e15;
-    }
-    if (!finite || t.slots.empty()) {
+    const double e[3] = {cam.eye[0], cam.eye[1], cam.eye[2]};
+    if (!prim_camera_usable(cam) || t.slots.empty()) {
         out.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
         return out;
     }
-    // a dummy slot (r*r = -inf) to pad the runs with; the tables end with pad slots
-    uint32_t pad = kPrimWalk;
-    for (size_t s = t.slots.size(); s-- > 0;)
-        if (t.slots[s].w == -INFINITY) {
-            pad = (uint32_t)s;
-            break;
-        }
+    const uint32_t pad = prim_pad_slot(t);
     if (pad == kPrimWalk) return out;
     std::vector<uint32_t> all(t.slots.size());
     std::iota(all.begin(), all.end(), 0u);

@@ -66,6 +66,13 @@ struct AccelTables {
 AccelTables build_accel(const float *centers4, const float *radii, uint32_t n, uint32_t cluster_k, uint32_t group,
                         uint32_t branching, uint32_t leaf_slots);
 
+// The tables of the same spheres (radii unchanged) at new centres, in place: the shape of t
+// stays -- slot order, orig, leaf membership, skip links, sibling order -- and slot centres,
+// pretest constants and every node's bound are recomputed with build_accel's arithmetic.
+// Empty string = done; else the reason (a non-finite centre, tables of another scene) with
+// t unchanged.  Centres of 1e15 and beyond are accepted and take the never-cull branches.
+std::string refit_accel(AccelTables &t, const float *centers4, const float *radii, uint32_t n);
+
 // Structural and containment checks of the tables the kernel relies on for
 // exactness and in-bounds loads; empty string = valid, else the first problem.
 std::string validate_accel(const AccelTables &t, const float *centers4, const float *radii, uint32_t n);
@@ -83,5 +90,10 @@ struct PrimListTables {
 };
 PrimListTables build_prim_lists(const AccelTables &t, const Camera &cam, uint32_t width, uint32_t height,
                                 uint32_t max_count);
+// Two of its conditions, shared with the device builder's host half (spt_update.cpp): the
+// camera is finite (eye below 1e15), and a dummy slot (r*r = -inf) of the tables to pad the
+// runs with (the tables end with pad slots; kPrimWalk: none).
+bool prim_camera_usable(const Camera &cam);
+uint32_t prim_pad_slot(const AccelTables &t);
 
 }  // namespace spt

@@ -503,10 +503,14 @@ int features_mark(spt_ctx *ctx, hipStream_t s)
 // size (none for trees walked lane by lane, which have no primary batches: casting their
 // freshly started paths against the lists cut config 5's node visits per ray 17.1 -> 12.7
 // but not its walk iterations or time).
-int rebuild_prim(spt_ctx *ctx)
+bool prim_wanted(const spt_ctx *ctx)
 {
-    const bool want = ctx->prim_enabled && ctx->scene_set && ctx->cam_set && ctx->params_set &&
-                      !spt::lane_walk_tree(ctx->accel);
+    return ctx->prim_enabled && ctx->scene_set && ctx->cam_set && ctx->params_set && !spt::lane_walk_tree(ctx->accel);
+}
+
+// what lists built now would be built for
+spt_ctx::PrimKey prim_key_now(const spt_ctx *ctx)
+{
     spt_ctx::PrimKey key{};
     for (int i = 0; i < 12; ++i) key.view[i] = ctx->cam.view[i];
     for (int i = 0; i < 3; ++i) key.eye[i] = ctx->cam.eye[i];
@@ -514,12 +518,26 @@ int rebuild_prim(spt_ctx *ctx)
     key.H = ctx->H;
     key.prim_max = ctx->prim_max;
     key.accel_gen = ctx->accel_gen;
+    key.refit_gen = ctx->refit_gen;
     key.valid = true;
+    return key;
+}
+
+// no lists: every primary batch walks the tree
+void prim_drop(spt_ctx *ctx)
+{
+    ctx->prim = spt::PrimLists{};
+    ctx->prim_blocks = ctx->prim_entries = ctx->prim_slots_n = 0;
+    ctx->prim_key = spt_ctx::PrimKey{};
+}
+
+int rebuild_prim(spt_ctx *ctx)
+{
+    const bool want = prim_wanted(ctx);
+    const spt_ctx::PrimKey key = prim_key_now(ctx);
     // the lists depend on the accel tables, the camera and the frame size only
     if (want && key.same(ctx->prim_key)) return SPT_OK;
-    ctx->prim = spt::PrimLists{};
-    ctx->prim_blocks = ctx->prim_entries = 0;
-    ctx->prim_key = spt_ctx::PrimKey{};
+    prim_drop(ctx);
     if (!want) return SPT_OK;
     spt::PrimListTables pl = spt::build_prim_lists(ctx->tables, ctx->cam, ctx->W, ctx->H, ctx->prim_max);
     ctx->prim_build_s = pl.seconds;
@@ -534,7 +552,7 @@ int rebuild_prim(spt_ctx *ctx)
     if (rc) return rc;
     ctx->prim = spt::PrimLists{ctx->d_prim_b8, ctx->d_prim_b4, ctx->d_prim_slots, pl.bw, 1u};
     for (const uint2 &b : pl.b8) ctx->prim_blocks += b.y != spt::kPrimWalk ? 1u : 0u;
-    ctx->prim_entries = (uint32_t)pl.slots.size();
+    ctx->prim_entries = ctx->prim_slots_n = (uint32_t)pl.slots.size();
     return SPT_OK;
 }
 
@@ -841,6 +859,8 @@ int spt_ctx_create(int device, spt_ctx **out)
     // liveness tests (tests/test_gpu_service.py)
     if (const char *e = env_var("SPT_PRIM_LISTS")) ctx->prim_enabled = std::atoi(e) != 0;
     if (const char *e = env_var("SPT_PRIM_MAX")) ctx->prim_max = (uint32_t)std::max(0, std::atoi(e));
+    if (const char *e = env_var("SPT_PRIM_DEVICE_SLOTS"))  // tests: the host fallback of spt_update_scene
+        ctx->prim_dev_slots = std::min(spt::kPrimDevSlots, (uint32_t)std::max(0, std::atoi(e)));
     if (const char *e = env_var("SPT_SVC_GRID_DIV")) ctx->svc.grid_div = (uint32_t)std::max(1, std::atoi(e));
     if (const char *e = env_var("SPT_SVC_TIMEOUT_MS")) ctx->svc.timeout_ms = std::max(1.0, std::atof(e));
     if (const char *e = env_var("SPT_SVC_DEBUG")) ctx->svc.debug = std::atoi(e) != 0;
@@ -929,7 +949,7 @@ void spt_ctx_destroy(spt_ctx *ctx)
     if (ctx->ad_count) (void)hipHostFree(ctx->ad_count);
     void *bufs[] = {ctx->d_shade, ctx->d_mat, ctx->d_slots, ctx->d_orig, ctx->d_nodes,
                     ctx->d_kpre, ctx->d_counters, ctx->d_frame8, ctx->d_prim_b8, ctx->d_prim_b4,
-                    ctx->d_prim_slots, ctx->d_ctab, ctx->ad_acc, ctx->ad_s12, ctx->ad_flags, ctx->ad_rects};
+                    ctx->d_prim_slots, ctx->d_prim_totals, ctx->d_ctab, ctx->ad_acc, ctx->ad_s12, ctx->ad_flags, ctx->ad_rects};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     for (Workspace &w : ctx->ws) {
@@ -948,6 +968,8 @@ void spt_ctx_destroy(spt_ctx *ctx)
     for (void *b : {(void *)ctx->d_tile, (void *)ctx->d_fullframe})
         if (b) (void)hipFree(b);
     if (ctx->frame_ev) (void)hipEventDestroy(ctx->frame_ev);
+    for (hipEvent_t e : ctx->upd_ev)
+        if (e) (void)hipEventDestroy(e);
     for (const auto &c : ctx->companions) (void)hipStreamDestroy(c.second);
     for (const spt_ctx::Masked &m : ctx->masked) {
         (void)hipStreamDestroy(m.stream);

@@ -16,6 +16,8 @@
 //                    it shares with spt_adaptive.hip and the host check
 //   spt_temporal.cpp temporal accumulation (spt_temporal_inverse, spt_temporal[_async],
 //                    spt_temporal_motion[_async])
+//   spt_update.cpp   scene updates (spt_update_scene: refit + the device list builder's host half,
+//                    spt_accel_refit_check, spt_prim_lists_read)
 //   spt_staging.cpp  the device staging of their blocking forms; spt_staging.h is its
 //                    HIP-free half (the plan: chunk size, offsets, total)
 // The context owns the device copy of the reference's global state (scene SoA, camera,
@@ -302,16 +304,26 @@ struct spt_ctx {
     struct PrimKey {
         float view[12], eye[3];
         uint32_t W, H, prim_max;
-        uint64_t accel_gen;
+        uint64_t accel_gen, refit_gen;
         bool valid;
         bool same(const PrimKey &o) const
         {
             return valid && o.valid && std::memcmp(view, o.view, sizeof view) == 0 &&
                    std::memcmp(eye, o.eye, sizeof eye) == 0 && W == o.W && H == o.H && prim_max == o.prim_max &&
-                   accel_gen == o.accel_gen;
+                   accel_gen == o.accel_gen && refit_gen == o.refit_gen;
         }
     } prim_key{};
     uint64_t accel_gen = 0;  // rebuild_accel count
+    // spt_update_scene's refits: the candidate lists follow the centres (PrimKey), the fold's
+    // colour table does not (shading table, slot order and depth only: ctab_gen is accel_gen's)
+    uint64_t refit_gen = 0;
+    // the device list builder (spt_update.cpp): its totals {8x8 blocks with a list, entries},
+    // the events around its launch, and the slot count above which the host builds instead
+    // (kPrimDevSlots, or SPT_PRIM_DEVICE_SLOTS if lower)
+    uint32_t *d_prim_totals = nullptr;
+    hipEvent_t upd_ev[2] = {};
+    uint32_t prim_dev_slots = spt::kPrimDevSlots;
+    uint32_t prim_slots_n = 0;  // entries of d_prim_slots in use (packed runs, or the fixed strides' span)
     uint32_t prim_blocks = 0, prim_entries = 0;  // 8x8 blocks with a list, list entries
     // diffuse sample codes (spt_internal.h diffuse_code): the slot count, and the halvings
     // after which every finite albedo of the scene is 0 (j saturates at min(bounces - 1, jz))
@@ -477,6 +489,10 @@ int spt_set_scene_one(spt_ctx *ctx, const float *centers4, const float *radii, c
 uint32_t even_strip(uint32_t height, uint32_t parts);
 int check_not_in_callback(spt_ctx *ctx);
 int rebuild_prim(spt_ctx *ctx);
+bool prim_wanted(const spt_ctx *ctx);
+spt_ctx::PrimKey prim_key_now(const spt_ctx *ctx);
+void prim_drop(spt_ctx *ctx);
+int spt_update_scene_one(spt_ctx *ctx, const float *centers4, const float view[16], const float eye[4], spt_update_info *info);
 int wait_own_renders(spt_ctx *ctx);
 int features_mark(spt_ctx *ctx, hipStream_t s);
 int rebuild_accel(spt_ctx *ctx);

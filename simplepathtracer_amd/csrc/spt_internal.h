@@ -645,4 +645,24 @@ struct TemporalArgs {
 };
 hipError_t launch_temporal(TemporalArgs a, bool motion, hipStream_t s);
 
+// ---- candidate lists built on the device (spt_primlists.hip; spt_update_scene) ----------
+// The PrimLists of the slot table `slots` (n_slots <= kPrimDevSlots, the kernel's LDS list)
+// for a finite camera and a frame of at most 65 535 columns and rows, in fixed-stride
+// storage: block b of level l (0: 8x8, 1: 8x4) owns entries [(l * nb8 + b) * stride, + stride)
+// of `out`, stride = roundup4(prim_max) >= prim_max.  b8 / b4: nb8 / nb4 entries
+// {first, count}, count kPrimWalk = walk; `pad` is a dummy slot of the table; totals[0] +=
+// 8x8 blocks with a list, totals[1] += list entries (zeroed by the caller).
+constexpr uint32_t kPrimDevSlots = 2048;
+struct PrimBuildArgs {
+    const float4 *slots;
+    uint32_t n_slots, pad;
+    Camera cam;
+    uint32_t W, H, prim_max, stride;
+    uint32_t bw, nb8;
+    uint2 *b8, *b4;
+    uint32_t *out;
+    uint32_t *totals;
+};
+hipError_t launch_prim_lists(const PrimBuildArgs &a, hipStream_t s);
+
 }  // namespace spt

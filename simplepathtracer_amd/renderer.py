@@ -107,6 +107,52 @@ class Context:
         s = np.ascontiguousarray(np.asarray(sky, np.float32).reshape(4))
         self._check(_native.lib().spt_set_camera(self._h, _p(v), _p(e), _p(s)))
 
+    def update_scene(self, centers=None, view=None, eye=None) -> dict:
+        """Move the spheres and / or the camera without a rebuild (spt_update_scene): `centers`
+        (n, 3) or (n, 4) floats in the scene's order (None: the spheres stay), `view` and `eye`
+        together (None: the camera stays; the sky stays either way).  The traversal tables are
+        refit and the primary-ray candidate lists built on the device; every later call
+        computes what it computes after set_scene with the moved centres and set_camera, bit
+        for bit.  Returns spt_update_info as a dict, with lists_reason as a word ('device',
+        'off', 'camera', 'slots', 'unchanged')."""
+        c4 = None
+        if centers is not None:
+            c = np.asarray(centers, np.float32)
+            if c.ndim != 2 or c.shape[1] not in (3, 4):
+                raise ValueError(f"centers: expected (n, 3) or (n, 4) floats, got shape {c.shape}")
+            c4 = np.zeros((len(c), 4), np.float32)
+            c4[:, :3] = c[:, :3]
+            n = getattr(getattr(self, "_scene", None), "n", None)
+            if n is not None and len(c4) != n:
+                raise ValueError(f"centers: {len(c4)} spheres, the scene has {n}")
+        if (view is None) != (eye is None):
+            raise ValueError("update_scene: view and eye come together")
+        v = None if view is None else _view16(view)
+        e = None if eye is None else _eye4(eye)
+        info = _native.UpdateInfo()
+        self._check(_native.lib().spt_update_scene(self._h, None if c4 is None else _p(c4), None if v is None else _p(v),
+                                                   None if e is None else _p(e), ctypes.byref(info)))
+        d = {k: getattr(info, k) for k, _ in _native.UpdateInfo._fields_}
+        d["lists_reason"] = _native.UPDATE_LISTS_REASONS.get(info.lists_reason, info.lists_reason)
+        return d
+
+    def prim_lists(self, which: int = 0):
+        """The context's primary-ray candidate lists (spt_prim_lists_read): which = 0 those its
+        device holds, which = 1 the host builder's for the current tables, camera and frame.
+        Returns (b8, b4, ids, orig, on): (blocks, 2) uint32 {first, count} per 8x8 / 8x4
+        block (count 0xFFFFFFFF: the block walks), the entries, the sphere of every slot."""
+        L = _native.lib()
+        w, h = self._frame
+        bw = (w + 7) // 8
+        b8 = np.zeros(2 * bw * ((h + 7) // 8), np.uint32)
+        b4 = np.zeros(2 * bw * ((h + 3) // 4), np.uint32)
+        counts = np.zeros(4, np.uint32)
+        self._check(L.spt_prim_lists_read(self._h, which, None, None, None, None, 0, _p(counts)))
+        cap = int(max(counts[0], counts[1], 1))
+        ids, orig = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32)
+        self._check(L.spt_prim_lists_read(self._h, which, _p(b8), _p(b4), _p(ids), _p(orig), cap, _p(counts)))
+        return b8.reshape(-1, 2), b4.reshape(-1, 2), ids[:counts[0]], orig[:counts[1]], bool(counts[3])
+
     def set_params(self, width: int, height: int, spp: int, bounces: int, seed: int = 1) -> None:
         self._check(_native.lib().spt_set_params(self._h, width, height, spp, bounces, seed))
         self._frame = (width, height)
@@ -697,13 +743,20 @@ class TemporalAccumulator:
     ping-pong pair) live in torch tensors on the context's device, and a frame is the
     device-pointer forms enqueued on one stream of the accumulator's own, then one copy of the
     returned image to the host: the history never crosses the host link.  The images are the
-    non-resident accumulator's, bit for bit."""
+    non-resident accumulator's, bit for bit.
+
+    With refit=True the frames after the first move the spheres and the camera through
+    Context.update_scene (the traversal tables refit, the candidate lists built on the device)
+    in place of set_scene and set_camera, while the scene's sphere count, radii, colours,
+    materials and fuzz stay as they were; a frame that changes any of them falls back to
+    set_scene.  The images are those of refit=False, bit for bit."""
 
     def __init__(self, ctx: Context, width, height, spp, bounces, seed=1, sky=INIT_COLOR, resident=False,
-                 **temporal_kwargs):
+                 refit=False, **temporal_kwargs):
         self.ctx, self.width, self.height, self.spp, self.bounces = ctx, int(width), int(height), int(spp), int(bounces)
         self.seed, self.sky, self.kwargs = int(seed), sky, temporal_kwargs
         self.resident = bool(resident)
+        self.refit = bool(refit)
         self._dev = None  # the resident tensors, made by the first resident frame
         self.reset()
 
@@ -712,10 +765,13 @@ class TemporalAccumulator:
         self.frame_index = 0
         self._history = None  # ((rgba, mom, feat, ids), view, eye); resident: (slot, view, eye)
         self._spheres = None  # (n, 4): {C.xyz, r} of the last frame(scene=...)'s scene
+        self._fixed = None    # refit: (radii, colors, materials, fuzz) of the scene the context's tables were built for
+        self._cam_set = False  # refit: this accumulator has set the camera (and with it the sky)
 
-    def _set_scene(self, scene):
-        """set_scene for frame(scene=...); returns the motion table against the previous
-        frame's scene, or None where there is none to follow."""
+    def _set_scene(self, scene, view, eye):
+        """set_scene for frame(scene=...) (refit: update_scene with the frame's camera, where
+        only the centres changed); returns the motion table against the previous frame's scene,
+        or None where there is none to follow, and whether the camera was moved as well."""
         now = np.concatenate([scene.centers[:, :3], scene.radii[:, None]], axis=1).astype(np.float32)
         motion = None
         if self._spheres is not None:
@@ -723,9 +779,19 @@ class TemporalAccumulator:
                 raise ValueError(f"frame: {len(now)} spheres now, {len(self._spheres)} in the previous frame's scene")
             if self._history is not None:
                 motion = np.ascontiguousarray(np.concatenate([now, self._spheres], axis=1))
-        self.ctx.set_scene(scene)
+        fixed = (scene.radii, scene.colors, scene.materials, scene.fuzz)
+        moved_camera = False
+        if self.refit and self._fixed is not None and all(np.array_equal(a, b) for a, b in zip(fixed, self._fixed)):
+            if self._cam_set:
+                self.ctx.update_scene(scene.centers, view, _eye4(eye))
+                moved_camera = True
+            else:
+                self.ctx.update_scene(scene.centers)
+        else:
+            self.ctx.set_scene(scene)
+            self._fixed = tuple(np.array(a, copy=True) for a in fixed) if self.refit else None
         self._spheres = now
-        return motion
+        return motion, moved_camera
 
     def frame(self, view, eye, denoise=None, scene=None) -> np.ndarray:
         """The accumulated (H, W, 4) image of the next frame seen through `view` from `eye`;
@@ -736,8 +802,13 @@ class TemporalAccumulator:
         frame's scene had them (sphere_motion; the same spheres in the same order: ValueError
         when the counts differ); the first scene given has none to follow."""
         c, w, h = self.ctx, self.width, self.height
-        motion = self._set_scene(scene) if scene is not None else None
-        c.set_camera(view, _eye4(eye), self.sky)
+        motion, moved_camera = self._set_scene(scene, view, eye) if scene is not None else (None, False)
+        if not moved_camera:
+            if self.refit and self._cam_set:
+                c.update_scene(None, view, _eye4(eye))
+            else:
+                c.set_camera(view, _eye4(eye), self.sky)
+                self._cam_set = True
         c.set_params(w, h, self.spp, self.bounces, self.seed + self.frame_index)
         kw = dict(self.kwargs) if motion is None else dict(self.kwargs, motion=motion)
         if self.resident:
