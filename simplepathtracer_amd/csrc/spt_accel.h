@@ -90,7 +90,7 @@ struct PrimListTables {
 };
 PrimListTables build_prim_lists(const AccelTables &t, const Camera &cam, uint32_t width, uint32_t height,
                                 uint32_t max_count);
-// Two of its conditions, shared with the device builder's host half (spt_update.cpp): the
+// Two of its conditions, shared with the plan of the device builder (spt_scenestate.cpp update_lists): the
 // camera is finite (eye below 1e15), and a dummy slot (r*r = -inf) of the tables to pad the
 // runs with (the tables end with pad slots; kPrimWalk: none).
 bool prim_camera_usable(const Camera &cam);

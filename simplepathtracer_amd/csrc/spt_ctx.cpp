@@ -1,5 +1,5 @@
-// spt_ctx.cpp -- context lifetime, setters (scene, camera, params, traversal shape), the scene's
-// device tables and primary-ray lists, stats (spt_host.h).
+// spt_ctx.cpp -- context lifetime, streams, grids, workspaces, timing and stats (spt_host.h); the
+// scene state a context holds is spt_scenestate.cpp's.
 #include "spt_host.h"
 
 namespace spt_api {
@@ -166,26 +166,6 @@ double busy_ms(const spt_ctx *ctx)
     return total;
 }
 
-// Halvings after which every finite albedo component a of the scene, as the diffuse code
-// rebuilds it (a * 0.5f, then * 0.5f per further bounce: spt_kernels.hip halve_n), is 0;
-// at most kCodeSat.  Saturating j there changes no colour (diffuse_code).
-uint32_t halvings_to_zero(const std::vector<float4> &shade)
-{
-    uint32_t jz = 0;
-    for (const float4 &s : shade)
-        for (float a : {s.x, s.y, s.z}) {
-            if (!std::isfinite(a)) continue;  // inf and NaN stay themselves
-            volatile float x = a * 0.5f;
-            uint32_t j = 0;
-            while (x != 0.f && j < spt::kCodeSat) {
-                x = x * 0.5f;
-                ++j;
-            }
-            jz = std::max(jz, j);
-        }
-    return jz;
-}
-
 // j's saturation of the diffuse codes at the context's depth: j <= bounces - 1 always
 uint32_t code_jmax(const spt_ctx *ctx)
 {
@@ -194,7 +174,7 @@ uint32_t code_jmax(const spt_ctx *ctx)
 
 spt::DeviceScene device_scene(const spt_ctx *ctx)
 {
-    return spt::DeviceScene{ctx->d_shade, ctx->d_mat, ctx->n, ctx->code_stride, code_jmax(ctx), ctx->accel};
+    return spt::DeviceScene{ctx->scene.d_shade, ctx->scene.d_mat, ctx->n, ctx->code_stride, code_jmax(ctx), ctx->accel};
 }
 
 int check_ready(spt_ctx *ctx)
@@ -366,100 +346,6 @@ int ensure_wavefront(spt_ctx *ctx, Workspace *w, uint32_t cap, uint32_t qcap)
     return SPT_OK;
 }
 
-// Traversal shape for the current scene: a 4-ary (3-ary above 512 spheres) tree of
-// boxes over 8-sphere clusters (config 2: 14 650 Msamples/s against 13 950 for round 1's flat list of
-// 4-sphere clusters under bounding spheres); the flat list remains
-// selectable (spt_set_cluster_tree(ctx, 0)).  Scenes of <= 32 spheres are tested
-// brute force (build_accel).
-struct Shape {
-    uint32_t k, branching, leaf_slots;
-};
-Shape resolve_shape(const spt_ctx *ctx)
-{
-    const bool tree = ctx->tree_branching == SPT_TREE_AUTO ? true : ctx->tree_branching >= 2;
-    Shape sh;
-    sh.k = ctx->cluster_k != SPT_CLUSTER_AUTO ? ctx->cluster_k : tree ? spt::kClusterSlots : spt::kFlatLeafSlots;
-    // auto: 4 children per node; 3 for large scenes, whose trees the LDS kernel walks
-    // lane by lane (config 5: 107 ms per frame against 110 for 4)
-    sh.branching = tree ? (ctx->tree_branching == SPT_TREE_AUTO ? (ctx->n > 512 ? 3u : 4u) : ctx->tree_branching) : 0u;
-    sh.leaf_slots = !tree && sh.k <= spt::kFlatLeafSlots ? spt::kFlatLeafSlots : spt::kClusterSlots;
-    return sh;
-}
-
-// Build and upload the hot-loop traversal tables (spt_accel.cpp) for the current scene.
-int rebuild_accel(spt_ctx *ctx)
-{
-    const auto t_start = std::chrono::steady_clock::now();
-    const uint32_t g = spt::render_group_size();
-    const Shape sh = resolve_shape(ctx);
-    spt::AccelTables t = spt::build_accel(ctx->h_centers.data(), ctx->h_radii.data(), ctx->n, sh.k, g, sh.branching,
-                                          sh.leaf_slots);
-    const std::string bad = spt::validate_accel(t, ctx->h_centers.data(), ctx->h_radii.data(), ctx->n);
-    if (!bad.empty()) return fail(ctx, SPT_ERR_STATE, "traversal tables invalid: %s", bad.c_str());
-    // a diffuse sample's code is 2 + j * slots + slot (diffuse_code); check_ready checks
-    // that the scene's codes fit at the frame's depth
-    const uint32_t jz = halvings_to_zero(ctx->h_shade);
-    if (!spt::code_layout_fits(t.slots.size(), 0))
-        return fail(ctx, SPT_ERR_ARG, "%zu sphere slots exceed the sample code space", t.slots.size());
-    // shading tables in slot order: the kernel keeps the winner's slot, not its index
-    std::vector<float4> shade(t.slots.size(), make_float4(0.f, 0.f, 0.f, 0.f));
-    std::vector<uint32_t> mat(t.slots.size(), SPT_SKYBOX);
-    for (size_t j = 0; j < t.slots.size(); ++j)
-        if (t.orig[j] != 0xFFFFFFFFu) {
-            shade[j] = ctx->h_shade[t.orig[j]];
-            mat[j] = ctx->h_mat[t.orig[j]];
-        }
-    // every stream: host calls and caller-stream renders may still read the tables
-    HIP_TRY(ctx, hipDeviceSynchronize());
-    int rc = upload(ctx, &ctx->d_slots, &ctx->slots_cap, t.slots);
-    if (!rc) rc = upload(ctx, &ctx->d_shade, &ctx->shade_cap, shade);
-    if (!rc) rc = upload(ctx, &ctx->d_mat, &ctx->mat_cap, mat);
-    if (!rc) rc = upload(ctx, &ctx->d_orig, &ctx->orig_cap, t.orig);
-    if (!rc) rc = upload(ctx, &ctx->d_nodes, &ctx->nodes_cap, t.nodes);
-    if (!rc) rc = upload(ctx, &ctx->d_kpre, &ctx->kpre_cap, t.kpre);
-    if (rc) return rc;
-    ctx->accel = spt::AccelView{ctx->d_slots, ctx->d_orig, ctx->d_nodes, t.always_groups, t.n_nodes,
-                                t.n_nodes > t.leaves ? 1u : 0u, t.leaf_slots, ctx->d_kpre, t.pre_cm};
-    ctx->code_stride = (uint32_t)std::max<size_t>(t.slots.size(), 1);
-    ctx->code_jz = jz;
-    ctx->tables = std::move(t);
-    ctx->accel_gen++;
-    ctx->accel_build_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
-    return SPT_OK;
-}
-
-// The fold's colour table (spt_codes.h) for the current scene tables and depth: one entry
-// per diffuse code, filled on the device by the arithmetic decode (ctab_fill_kernel).  It
-// depends on the shading table, the slot order (code_stride) and jmax only, which the scene,
-// cluster and params setters change: they leave the table stale (ctab_valid), and the first
-// launched render after them (render_impl) calls this; nothing is done while the table
-// stands.  Like the scene uploads it waits for the device on both sides: launches in flight
-// on any stream may read the old table, and the launches enqueued after it on any stream
-// read the new one.
-bool ctab_valid(const spt_ctx *ctx)
-{
-    return ctx->ctab_n != 0 && ctx->ctab_gen == ctx->accel_gen && ctx->ctab_jmax == code_jmax(ctx);
-}
-
-int rebuild_ctab(spt_ctx *ctx)
-{
-    const uint32_t jmax = code_jmax(ctx);
-    if (ctx->ctab_gen == ctx->accel_gen && ctx->ctab_jmax == jmax) return SPT_OK;
-    if (int rc = svc_end(ctx)) return rc;  // a resident session would hold the synchronisation
-    ctx->ctab_n = 0;
-    ctx->ctab_gen = ctx->accel_gen;
-    ctx->ctab_jmax = jmax;
-    if (!spt::ctab_fits(ctx->code_stride, jmax) || !spt::code_layout_fits(ctx->code_stride, jmax)) return SPT_OK;
-    const uint32_t n = (uint32_t)spt::ctab_entries(ctx->code_stride, jmax);
-    HIP_TRY(ctx, hipDeviceSynchronize());
-    if (int rc = ensure(ctx, &ctx->d_ctab, &ctx->ctab_cap, n)) return rc;
-    spt::FoldArgs fa = fold_args(ctx, nullptr, 1u);
-    HIP_TRY(ctx, spt::launch_ctab_fill(fa, ctx->d_ctab, n, nullptr));
-    HIP_TRY(ctx, hipStreamSynchronize(nullptr));
-    ctx->ctab_n = n;
-    return SPT_OK;
-}
-
 // Wait for every render launch this context has enqueued (on any stream) -- not for the
 // device: unrelated work of the process (torch kernels, RCCL) keeps running.  The feature
 // kernels (spt_features.hip) read the candidate lists on caller streams as renders do:
@@ -499,63 +385,6 @@ int features_mark(spt_ctx *ctx, hipStream_t s)
     return SPT_OK;
 }
 
-// Build and upload the primary-ray candidate lists for the current scene, camera and frame
-// size (none for trees walked lane by lane, which have no primary batches: casting their
-// freshly started paths against the lists cut config 5's node visits per ray 17.1 -> 12.7
-// but not its walk iterations or time).
-bool prim_wanted(const spt_ctx *ctx)
-{
-    return ctx->prim_enabled && ctx->scene_set && ctx->cam_set && ctx->params_set && !spt::lane_walk_tree(ctx->accel);
-}
-
-// what lists built now would be built for
-spt_ctx::PrimKey prim_key_now(const spt_ctx *ctx)
-{
-    spt_ctx::PrimKey key{};
-    for (int i = 0; i < 12; ++i) key.view[i] = ctx->cam.view[i];
-    for (int i = 0; i < 3; ++i) key.eye[i] = ctx->cam.eye[i];
-    key.W = ctx->W;
-    key.H = ctx->H;
-    key.prim_max = ctx->prim_max;
-    key.accel_gen = ctx->accel_gen;
-    key.refit_gen = ctx->refit_gen;
-    key.valid = true;
-    return key;
-}
-
-// no lists: every primary batch walks the tree
-void prim_drop(spt_ctx *ctx)
-{
-    ctx->prim = spt::PrimLists{};
-    ctx->prim_blocks = ctx->prim_entries = ctx->prim_slots_n = 0;
-    ctx->prim_key = spt_ctx::PrimKey{};
-}
-
-int rebuild_prim(spt_ctx *ctx)
-{
-    const bool want = prim_wanted(ctx);
-    const spt_ctx::PrimKey key = prim_key_now(ctx);
-    // the lists depend on the accel tables, the camera and the frame size only
-    if (want && key.same(ctx->prim_key)) return SPT_OK;
-    prim_drop(ctx);
-    if (!want) return SPT_OK;
-    spt::PrimListTables pl = spt::build_prim_lists(ctx->tables, ctx->cam, ctx->W, ctx->H, ctx->prim_max);
-    ctx->prim_build_s = pl.seconds;
-    ctx->prim_builds++;
-    ctx->prim_key = key;
-    if (!pl.on) return SPT_OK;
-    // this context's renders in flight may still read the previous lists
-    if (int rc = wait_own_renders(ctx)) return rc;
-    int rc = upload(ctx, &ctx->d_prim_b8, &ctx->prim_b8_cap, pl.b8);
-    if (!rc) rc = upload(ctx, &ctx->d_prim_b4, &ctx->prim_b4_cap, pl.b4);
-    if (!rc) rc = upload(ctx, &ctx->d_prim_slots, &ctx->prim_slots_cap, pl.slots);
-    if (rc) return rc;
-    ctx->prim = spt::PrimLists{ctx->d_prim_b8, ctx->d_prim_b4, ctx->d_prim_slots, pl.bw, 1u};
-    for (const uint2 &b : pl.b8) ctx->prim_blocks += b.y != spt::kPrimWalk ? 1u : 0u;
-    ctx->prim_entries = ctx->prim_slots_n = (uint32_t)pl.slots.size();
-    return SPT_OK;
-}
-
 // Setters must not run from a progress callback of the same context (the render in
 // progress reads the state they change).
 int check_not_in_callback(spt_ctx *ctx)
@@ -582,111 +411,8 @@ uint32_t even_strip(uint32_t height, uint32_t parts)
     return 1u;
 }
 
-// Setters of one context; the exported setters apply them to every member device.
-int spt_set_scene_one(spt_ctx *ctx, const float *centers4, const float *radii, const float *colors4,
-                  const uint8_t *materials, const float *fuzz, uint32_t n)
-{
-    if (!ctx) return fail(nullptr, SPT_ERR_ARG, "null context");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    if (int rc_ = svc_end(ctx)) return rc_;  // the session holds the state this setter changes
-    ctx->gen++;                              // a read-ahead frame of the old state is stale
-    if (n > 0 && (!centers4 || !radii || !colors4 || !materials || !fuzz))
-        return fail(ctx, SPT_ERR_ARG, "null scene array");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    std::vector<float4> shade(n);
-    std::vector<uint32_t> mat(n);
-    for (uint32_t i = 0; i < n; ++i) {
-        shade[i] = make_float4(colors4[4 * i], colors4[4 * i + 1], colors4[4 * i + 2], fuzz[i]);
-        mat[i] = materials[i];
-    }
-    ctx->h_shade = std::move(shade);
-    ctx->h_mat = std::move(mat);
-    ctx->h_centers.assign(centers4, centers4 + 4 * (size_t)n);
-    ctx->h_radii.assign(radii, radii + n);
-    ctx->n = n;
-    int rc = rebuild_accel(ctx);
-    if (rc) return rc;
-    ctx->scene_set = true;
-    return rebuild_prim(ctx);
-}
-
-int spt_set_camera_one(spt_ctx *ctx, const float view[16], const float eye[4], const float sky[4])
-{
-    if (!ctx) return fail(nullptr, SPT_ERR_ARG, "null context");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    if (int rc_ = svc_end(ctx)) return rc_;  // the session holds the state this setter changes
-    ctx->gen++;                              // a read-ahead frame of the old state is stale
-    if (!view || !eye || !sky) return fail(ctx, SPT_ERR_ARG, "null camera array");
-    for (int j = 12; j < 16; ++j)
-        if (view[j] != 0.0f)
-            return fail(ctx, SPT_ERR_ARG, "viewMatrix row 3 must be zero (CreateCameraBasisMatrix, Math.hpp:204-208)");
-    for (int j = 0; j < 12; ++j) ctx->cam.view[j] = view[j];
-    for (int j = 0; j < 3; ++j) {
-        ctx->cam.eye[j] = eye[j];
-        ctx->cam.sky[j] = sky[j];
-    }
-    ctx->cam_set = true;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return rebuild_prim(ctx);
-}
-
-int spt_set_params_one(spt_ctx *ctx, uint32_t width, uint32_t height, uint32_t spp, uint32_t bounces, uint64_t seed)
-{
-    if (!ctx) return fail(nullptr, SPT_ERR_ARG, "null context");
-    std::unique_lock<std::mutex> lk(ctx->mu);
-    if (int rc_ = svc_end(ctx)) return rc_;  // the session holds the state this setter changes
-    ctx->gen++;                              // a read-ahead frame of the old state is stale
-    if (width == 0 || height == 0) return fail(ctx, SPT_ERR_ARG, "empty frame %ux%u", width, height);
-    if ((uint64_t)width * height * 3 > 0xFFFFFFFFull)
-        return fail(ctx, SPT_ERR_ARG, "frame %ux%u overflows the reference's uint32 g_size", width, height);
-    if (spp == 0) return fail(ctx, SPT_ERR_ARG, "spp must be >= 1 (1.f/0 samples)");
-    if (bounces == 0) return fail(ctx, SPT_ERR_ARG, "bounces must be >= 1 (--bounceCount never reaches 0)");
-    ctx->W = width;
-    ctx->H = height;
-    ctx->spp = spp;
-    ctx->bounces = bounces;
-    ctx->seed = seed;
-    ctx->params_set = true;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int rc = rebuild_prim(ctx);
-    // the drop-in (spt_prepare_dropin) renders its first frame through the tiling read-ahead:
-    // its page-locked frame now, with the setup, not in that frame.  Last, once the context
-    // is whole again, as it may wait unlocked for serves in progress; best effort: else at
-    // the first tile-shaped call
-    if (ctx->spec.st.arm_first() && ctx->readahead) (void)spec_frame_bytes(ctx, lk, (size_t)width * height * 3);
-    return rc;
-}
-
-int spt_set_cluster_size_one(spt_ctx *ctx, uint32_t k)
-{
-    if (!ctx) return fail(nullptr, SPT_ERR_ARG, "null context");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    if (int rc_ = svc_end(ctx)) return rc_;  // the session holds the state this setter changes
-    ctx->gen++;                              // a read-ahead frame of the old state is stale
-    if (k > spt::kClusterSlots && k != SPT_CLUSTER_AUTO)
-        return fail(ctx, SPT_ERR_ARG, "cluster size %u > %u", k, spt::kClusterSlots);
-    ctx->cluster_k = k;
-    if (!ctx->scene_set) return SPT_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = rebuild_accel(ctx);
-    return rc ? rc : rebuild_prim(ctx);
-}
-
-int spt_set_cluster_tree_one(spt_ctx *ctx, uint32_t branching)
-{
-    if (!ctx) return fail(nullptr, SPT_ERR_ARG, "null context");
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    if (int rc_ = svc_end(ctx)) return rc_;  // the session holds the state this setter changes
-    ctx->gen++;                              // a read-ahead frame of the old state is stale
-    if (branching == 1 || (branching > 64 && branching != SPT_TREE_AUTO))
-        return fail(ctx, SPT_ERR_ARG, "tree branching %u not in {0, 2..64, SPT_TREE_AUTO}", branching);
-    ctx->tree_branching = branching;
-    if (!ctx->scene_set) return SPT_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = rebuild_accel(ctx);
-    return rc ? rc : rebuild_prim(ctx);
-}
-
+// Setters of one context; the exported setters apply them to every member device (those of
+// the scene state: spt_scenestate.cpp).
 int spt_set_engine_one(spt_ctx *ctx, int engine)
 {
     if (!ctx) return fail(nullptr, SPT_ERR_ARG, "null context");
@@ -739,12 +465,12 @@ int stats_one(spt_ctx *ctx, spt_stats *out)
     out->svc_grid_blocks = svc_session_grid(ctx);
     out->svc_flow_restarts = ctx->svc.flow_restarts;
     out->svc_closing_restarts = ctx->svc.closing_restarts;
-    out->prim_list_blocks = ctx->prim_blocks;
-    out->prim_list_entries = ctx->prim_entries;
-    out->prim_list_build_ms = ctx->prim_build_s * 1e3;
-    out->prim_list_builds = ctx->prim_builds;
-    out->accel_build_ms = ctx->accel_build_s * 1e3;
-    out->fold_table_entries = ctab_valid(ctx) ? ctx->ctab_n : 0u;
+    out->prim_list_blocks = ctx->scene.prim_blocks;
+    out->prim_list_entries = ctx->scene.prim_entries;
+    out->prim_list_build_ms = ctx->scene.prim_build_s * 1e3;
+    out->prim_list_builds = ctx->scene.prim_builds;
+    out->accel_build_ms = ctx->scene.accel_build_s * 1e3;
+    out->fold_table_entries = ctab_valid(ctx) ? ctx->scene.ctab_n : 0u;
     return SPT_OK;
 }
 
@@ -947,9 +673,10 @@ void spt_ctx_destroy(spt_ctx *ctx)
     if (ctx->ref_ev) (void)hipEventDestroy(ctx->ref_ev);
     if (ctx->ad_done) (void)hipEventDestroy(ctx->ad_done);
     if (ctx->ad_count) (void)hipHostFree(ctx->ad_count);
-    void *bufs[] = {ctx->d_shade, ctx->d_mat, ctx->d_slots, ctx->d_orig, ctx->d_nodes,
-                    ctx->d_kpre, ctx->d_counters, ctx->d_frame8, ctx->d_prim_b8, ctx->d_prim_b4,
-                    ctx->d_prim_slots, ctx->d_prim_totals, ctx->d_ctab, ctx->ad_acc, ctx->ad_s12, ctx->ad_flags, ctx->ad_rects};
+    const SceneState &sc = ctx->scene;
+    void *bufs[] = {sc.d_shade, sc.d_mat, sc.d_slots, sc.d_orig, sc.d_nodes, sc.d_kpre, sc.d_prim_b8, sc.d_prim_b4,
+                    sc.d_prim_slots, sc.d_prim_totals, sc.d_ctab, ctx->d_counters, ctx->d_frame8, ctx->ad_acc, ctx->ad_s12,
+                    ctx->ad_flags, ctx->ad_rects};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     for (Workspace &w : ctx->ws) {
@@ -968,7 +695,7 @@ void spt_ctx_destroy(spt_ctx *ctx)
     for (void *b : {(void *)ctx->d_tile, (void *)ctx->d_fullframe})
         if (b) (void)hipFree(b);
     if (ctx->frame_ev) (void)hipEventDestroy(ctx->frame_ev);
-    for (hipEvent_t e : ctx->upd_ev)
+    for (hipEvent_t e : sc.upd_ev)
         if (e) (void)hipEventDestroy(e);
     for (const auto &c : ctx->companions) (void)hipStreamDestroy(c.second);
     for (const spt_ctx::Masked &m : ctx->masked) {
@@ -999,32 +726,6 @@ const char *spt_last_error(const spt_ctx *ctx)
 {
     if (ctx) return ctx->err.c_str();
     return g_thread_error.c_str();
-}
-
-int spt_set_scene(spt_ctx *ctx, const float *centers4, const float *radii, const float *colors4,
-                  const uint8_t *materials, const float *fuzz, uint32_t n)
-{
-    return for_members(ctx, [&](spt_ctx *c) { return spt_set_scene_one(c, centers4, radii, colors4, materials, fuzz, n); });
-}
-
-int spt_set_camera(spt_ctx *ctx, const float view[16], const float eye[4], const float sky[4])
-{
-    return for_members(ctx, [&](spt_ctx *c) { return spt_set_camera_one(c, view, eye, sky); });
-}
-
-int spt_set_params(spt_ctx *ctx, uint32_t width, uint32_t height, uint32_t spp, uint32_t bounces, uint64_t seed)
-{
-    return for_members(ctx, [&](spt_ctx *c) { return spt_set_params_one(c, width, height, spp, bounces, seed); });
-}
-
-int spt_set_cluster_size(spt_ctx *ctx, uint32_t k)
-{
-    return for_members(ctx, [&](spt_ctx *c) { return spt_set_cluster_size_one(c, k); });
-}
-
-int spt_set_cluster_tree(spt_ctx *ctx, uint32_t branching)
-{
-    return for_members(ctx, [&](spt_ctx *c) { return spt_set_cluster_tree_one(c, branching); });
 }
 
 int spt_prepare_dropin(spt_ctx *ctx)
@@ -1061,54 +762,6 @@ int spt_set_reserved_cus(spt_ctx *ctx, uint32_t n)
         c->reserve_cus = n;
         return SPT_OK;
     });
-}
-
-int spt_accel_check(const float *centers4, const float *radii, uint32_t n, uint32_t cluster_k, uint32_t branching,
-                    uint32_t *out_nodes)
-{
-    if (n > 0 && (!centers4 || !radii)) return fail(nullptr, SPT_ERR_ARG, "null scene array");
-    if (cluster_k > spt::kClusterSlots) return fail(nullptr, SPT_ERR_ARG, "cluster size %u > %u", cluster_k, spt::kClusterSlots);
-    if (branching == 1) return fail(nullptr, SPT_ERR_ARG, "tree branching 1");
-    const uint32_t k = cluster_k == 0 ? 0u : cluster_k;
-    const uint32_t leaf = branching == 0 && k <= spt::kFlatLeafSlots ? spt::kFlatLeafSlots : spt::kClusterSlots;
-    const spt::AccelTables t = spt::build_accel(centers4, radii, n, k, spt::render_group_size(), branching, leaf);
-    const std::string bad = spt::validate_accel(t, centers4, radii, n);
-    if (!bad.empty()) return fail(nullptr, SPT_ERR_STATE, "traversal tables invalid: %s", bad.c_str());
-    if (out_nodes) *out_nodes = t.n_nodes;
-    return SPT_OK;
-}
-
-int spt_prim_lists_check(const float *centers4, const float *radii, uint32_t n, const float view[16], const float eye[4],
-                         uint32_t width, uint32_t height, uint32_t max_count, uint32_t *blocks8, uint32_t *blocks4,
-                         uint32_t *slot_ids, uint32_t *slot_orig, uint32_t cap, uint32_t *counts)
-{
-    if (n > 0 && (!centers4 || !radii)) return fail(nullptr, SPT_ERR_ARG, "null scene array");
-    if (!view || !eye || !counts || width == 0 || height == 0) return fail(nullptr, SPT_ERR_ARG, "bad arguments");
-    // the default traversal shape (resolve_shape with both settings on auto)
-    const uint32_t branching = n > 512 ? 3u : 4u;
-    const spt::AccelTables t =
-        spt::build_accel(centers4, radii, n, spt::kClusterSlots, spt::render_group_size(), branching, spt::kClusterSlots);
-    spt::Camera cam{};
-    for (int j = 0; j < 12; ++j) cam.view[j] = view[j];
-    for (int j = 0; j < 3; ++j) cam.eye[j] = eye[j];
-    const spt::PrimListTables pl = spt::build_prim_lists(t, cam, width, height, max_count);
-    counts[0] = (uint32_t)pl.slots.size();
-    counts[1] = (uint32_t)t.slots.size();
-    counts[2] = pl.bw;
-    counts[3] = pl.on ? 1u : 0u;
-    if ((slot_ids && cap < pl.slots.size()) || (slot_orig && cap < t.slots.size()))
-        return fail(nullptr, SPT_ERR_ARG, "capacity %u < %zu list entries / %zu slots", cap, pl.slots.size(), t.slots.size());
-    for (size_t i = 0; blocks8 && i < pl.b8.size(); ++i) {
-        blocks8[2 * i] = pl.b8[i].x;
-        blocks8[2 * i + 1] = pl.b8[i].y;
-    }
-    for (size_t i = 0; blocks4 && i < pl.b4.size(); ++i) {
-        blocks4[2 * i] = pl.b4[i].x;
-        blocks4[2 * i + 1] = pl.b4[i].y;
-    }
-    if (slot_ids) std::copy(pl.slots.begin(), pl.slots.end(), slot_ids);
-    if (slot_orig) std::copy(t.orig.begin(), t.orig.end(), slot_orig);
-    return SPT_OK;
 }
 
 int spt_set_engine(spt_ctx *ctx, int engine)

@@ -1,6 +1,10 @@
 // spt_host.h -- the host side of the C ABI (include/spt_hip.h), shared by its translation
 // units (round 6: spt_api.cpp split along its sections, no behaviour change):
-//   spt_ctx.cpp      context, setters, scene / accel / primary-list uploads, stats
+//   spt_ctx.cpp      context lifetime, streams, grids, workspaces, timing, stats
+//   spt_scenestate.cpp scene state (SceneState below): the scene, camera, params and shape setters,
+//                    spt_update_scene, the one path of traversal tables and the one path of
+//                    candidate lists to the device, the fold's colour table, the host-only
+//                    checks; spt_primplan.h is the lists' HIP-free plan
 //   spt_render.cpp   render_impl (render + fold launches), host calls, rows / samples entry points
 //   spt_batch.cpp    batched host calls (render_batched, launch_batch)
 //   spt_readahead.cpp the tiling read-ahead's HIP half (SpecFrame); spt_readahead.h is its
@@ -16,8 +20,6 @@
 //                    it shares with spt_adaptive.hip and the host check
 //   spt_temporal.cpp temporal accumulation (spt_temporal_inverse, spt_temporal[_async],
 //                    spt_temporal_motion[_async])
-//   spt_update.cpp   scene updates (spt_update_scene: refit + the device list builder's host half,
-//                    spt_accel_refit_check, spt_prim_lists_read)
 //   spt_staging.cpp  the device staging of their blocking forms; spt_staging.h is its
 //                    HIP-free half (the plan: chunk size, offsets, total)
 // The context owns the device copy of the reference's global state (scene SoA, camera,
@@ -30,6 +32,7 @@
 #include "spt_accel.h"
 #include "spt_adaptive.h"
 #include "spt_internal.h"
+#include "spt_primplan.h"
 #include "spt_readahead.h"
 #include "spt_staging.h"
 
@@ -231,6 +234,66 @@ struct Service {
     double kernel_ms = 0;  // summed session spans
     unsigned long long *d_trace = nullptr;  // SPT_SVC_TRACE: printed by svc_end
 };
+// The scene state of a context: traversal tables and primary-ray candidate lists on the device
+// with their capacities, the host tables and scene arrays they are built from, what they were
+// built for, and their counters.  spt_scenestate.cpp alone writes it (put_tables, update_lists,
+// rebuild_ctab, spt_set_scene); the other files read it or free it (spt_ctx_destroy).
+struct SceneState {
+    // traversal tables on the device (spt_accel.h; shade and mat in slot order)
+    float4 *d_shade = nullptr, *d_slots = nullptr;
+    spt::AccelNode *d_nodes = nullptr;
+    uint32_t *d_mat = nullptr, *d_orig = nullptr;
+    float *d_kpre = nullptr;
+    size_t shade_cap = 0, mat_cap = 0, slots_cap = 0, orig_cap = 0, nodes_cap = 0, kpre_cap = 0;
+    // their host copy: replaced once every upload of a build has succeeded, refit in place
+    spt::AccelTables tables;
+    // host copy of the scene, to rebuild the tables: the hit geometry (the centres follow a
+    // refit), {r, g, b, fuzz} and the material per sphere
+    std::vector<float> h_centers, h_radii;
+    std::vector<float4> h_shade;
+    std::vector<uint32_t> h_mat;
+    uint64_t accel_gen = 0;  // builds of the tables (put_tables)
+    // spt_update_scene's refits: the candidate lists follow the centres (PrimKey), the fold's
+    // colour table does not (shading table, slot order and depth only: ctab_gen is accel_gen's)
+    uint64_t refit_gen = 0;
+    double accel_build_s = 0;  // host time of the last build (build, check, upload)
+
+    // candidate lists on the device (spt_internal.h PrimLists; ctx->prim is their view)
+    uint2 *d_prim_b8 = nullptr, *d_prim_b4 = nullptr;
+    uint32_t *d_prim_slots = nullptr;
+    size_t prim_b8_cap = 0, prim_b4_cap = 0, prim_slots_cap = 0;
+    // the device list builder (spt_primlists.hip): its totals {8x8 blocks with a list,
+    // entries} and the events around its launch
+    uint32_t *d_prim_totals = nullptr;
+    hipEvent_t upd_ev[2] = {};
+    // what the lists were built for (update_lists skips a rebuild when nothing the lists
+    // depend on changed: spp, depth and seed setters do not touch them)
+    struct PrimKey {
+        float view[12], eye[3];
+        uint32_t W, H, prim_max;
+        uint64_t accel_gen, refit_gen;
+        bool valid;
+        bool same(const PrimKey &o) const
+        {
+            return valid && o.valid && std::memcmp(view, o.view, sizeof view) == 0 &&
+                   std::memcmp(eye, o.eye, sizeof eye) == 0 && W == o.W && H == o.H && prim_max == o.prim_max &&
+                   accel_gen == o.accel_gen && refit_gen == o.refit_gen;
+        }
+    } prim_key{};
+    uint32_t prim_slots_n = 0;  // entries of d_prim_slots in use (packed runs, or the fixed strides' span)
+    uint32_t prim_blocks = 0, prim_entries = 0;  // 8x8 blocks with a list, list entries
+    uint64_t prim_builds = 0;
+    double prim_build_s = 0;  // the last build: host time of the host builder, event time of the kernel
+
+    // the fold's colour table (spt_codes.h): ctab_n entries for codes up to jmax = ctab_jmax,
+    // rebuilt by rebuild_ctab (the first launched render after the scene tables or jmax
+    // changed); ctab_n = 0: none (above kCtabMaxBytes), the kernels decode arithmetically
+    float4 *d_ctab = nullptr;
+    size_t ctab_cap = 0;
+    uint32_t ctab_n = 0, ctab_jmax = 0;
+    uint64_t ctab_gen = 0;  // accel_gen it was built for (0: never)
+};
+
 // One job of a publication: a region (rows or interleaved strips, columns) at spp_batch
 // samples from sample s0, its slots at slot_local of the publication's ring region.
 struct SvcJobSpec {
@@ -279,13 +342,10 @@ struct spt_ctx {
     int svc_per_cu = 1;     // the occupancy's blocks per CU the session grids derive from
     uint32_t last_grid = 0, last_block = 0;  // shape of the most recent render launch
 
-    // scene (Globals.hpp:31-37)
-    float4 *d_shade = nullptr, *d_slots = nullptr;
-    spt::AccelNode *d_nodes = nullptr;
-    uint32_t *d_mat = nullptr, *d_orig = nullptr;
-    float *d_kpre = nullptr;
-    size_t shade_cap = 0, mat_cap = 0, slots_cap = 0, orig_cap = 0, nodes_cap = 0, kpre_cap = 0;
-    spt::AccelTables tables;
+    // scene (Globals.hpp:31-37): the tables, lists and counters are `scene` (SceneState above),
+    // which spt_scenestate.cpp alone writes, as it does the views the kernels take (accel, prim)
+    // and n, code_stride, code_jz, cam and the frame below
+    SceneState scene;
     uint32_t n = 0;
     // primary-ray candidate lists (spt_internal.h PrimLists), rebuilt by the setters once
     // scene, camera and frame are set; SPT_PRIM_LISTS=0 turns them off, SPT_PRIM_MAX caps a
@@ -293,53 +353,13 @@ struct spt_ctx {
     bool prim_enabled = true;
     uint32_t prim_max = 24;
     spt::PrimLists prim{};
-    uint2 *d_prim_b8 = nullptr, *d_prim_b4 = nullptr;
-    uint32_t *d_prim_slots = nullptr;
-    size_t prim_b8_cap = 0, prim_b4_cap = 0, prim_slots_cap = 0;
-    double prim_build_s = 0;  // host time of the last build
-    uint64_t prim_builds = 0;
-    double accel_build_s = 0;  // host time of the last rebuild_accel (build, check, upload)
-    // what the lists were built for (rebuild_prim skips a rebuild when nothing the lists
-    // depend on changed: spp, depth and seed setters do not touch them)
-    struct PrimKey {
-        float view[12], eye[3];
-        uint32_t W, H, prim_max;
-        uint64_t accel_gen, refit_gen;
-        bool valid;
-        bool same(const PrimKey &o) const
-        {
-            return valid && o.valid && std::memcmp(view, o.view, sizeof view) == 0 &&
-                   std::memcmp(eye, o.eye, sizeof eye) == 0 && W == o.W && H == o.H && prim_max == o.prim_max &&
-                   accel_gen == o.accel_gen && refit_gen == o.refit_gen;
-        }
-    } prim_key{};
-    uint64_t accel_gen = 0;  // rebuild_accel count
-    // spt_update_scene's refits: the candidate lists follow the centres (PrimKey), the fold's
-    // colour table does not (shading table, slot order and depth only: ctab_gen is accel_gen's)
-    uint64_t refit_gen = 0;
-    // the device list builder (spt_update.cpp): its totals {8x8 blocks with a list, entries},
-    // the events around its launch, and the slot count above which the host builds instead
-    // (kPrimDevSlots, or SPT_PRIM_DEVICE_SLOTS if lower)
-    uint32_t *d_prim_totals = nullptr;
-    hipEvent_t upd_ev[2] = {};
+    // the slot count above which the host builds the lists of a scene update (kPrimDevSlots,
+    // the device builder's LDS list, or SPT_PRIM_DEVICE_SLOTS if lower)
     uint32_t prim_dev_slots = spt::kPrimDevSlots;
-    uint32_t prim_slots_n = 0;  // entries of d_prim_slots in use (packed runs, or the fixed strides' span)
-    uint32_t prim_blocks = 0, prim_entries = 0;  // 8x8 blocks with a list, list entries
     // diffuse sample codes (spt_internal.h diffuse_code): the slot count, and the halvings
     // after which every finite albedo of the scene is 0 (j saturates at min(bounces - 1, jz))
     uint32_t code_stride = 1, code_jz = 0;
-    // the fold's colour table (spt_codes.h): ctab_n entries for codes up to jmax = ctab_jmax,
-    // rebuilt by rebuild_ctab (the first launched render after the scene tables or jmax
-    // changed); ctab_n = 0: none (above kCtabMaxBytes), the kernels decode arithmetically
-    float4 *d_ctab = nullptr;
-    size_t ctab_cap = 0;
-    uint32_t ctab_n = 0, ctab_jmax = 0;
-    uint64_t ctab_gen = 0;  // accel_gen it was built for (0: never)
     bool scene_set = false;
-    // host copy of the hit geometry, to rebuild the traversal tables
-    std::vector<float> h_centers, h_radii;
-    std::vector<float4> h_shade;  // {r, g, b, fuzz} per sphere
-    std::vector<uint32_t> h_mat;
     uint32_t cluster_k = SPT_CLUSTER_AUTO;  // members per culling cluster; 0 = brute force
     uint32_t tree_branching = SPT_TREE_AUTO;  // children per inner node; 0 = flat cluster list
     int engine = SPT_ENGINE_MEGAKERNEL;
@@ -481,21 +501,10 @@ namespace spt_api {
 
 int spt_set_workspace_one(spt_ctx *ctx, uint64_t bytes);
 int spt_set_engine_one(spt_ctx *ctx, int engine);
-int spt_set_cluster_tree_one(spt_ctx *ctx, uint32_t branching);
-int spt_set_cluster_size_one(spt_ctx *ctx, uint32_t k);
-int spt_set_params_one(spt_ctx *ctx, uint32_t width, uint32_t height, uint32_t spp, uint32_t bounces, uint64_t seed);
-int spt_set_camera_one(spt_ctx *ctx, const float view[16], const float eye[4], const float sky[4]);
-int spt_set_scene_one(spt_ctx *ctx, const float *centers4, const float *radii, const float *colors4, const uint8_t *materials, const float *fuzz, uint32_t n);
 uint32_t even_strip(uint32_t height, uint32_t parts);
 int check_not_in_callback(spt_ctx *ctx);
-int rebuild_prim(spt_ctx *ctx);
-bool prim_wanted(const spt_ctx *ctx);
-spt_ctx::PrimKey prim_key_now(const spt_ctx *ctx);
-void prim_drop(spt_ctx *ctx);
-int spt_update_scene_one(spt_ctx *ctx, const float *centers4, const float view[16], const float eye[4], spt_update_info *info);
 int wait_own_renders(spt_ctx *ctx);
 int features_mark(spt_ctx *ctx, hipStream_t s);
-int rebuild_accel(spt_ctx *ctx);
 int rebuild_ctab(spt_ctx *ctx);
 bool ctab_valid(const spt_ctx *ctx);
 int ensure_wavefront(spt_ctx *ctx, Workspace *w, uint32_t cap, uint32_t qcap);
@@ -509,7 +518,6 @@ uint64_t fmix64(uint64_t z);
 int check_ready(spt_ctx *ctx);
 spt::DeviceScene device_scene(const spt_ctx *ctx);
 uint32_t code_jmax(const spt_ctx *ctx);
-uint32_t halvings_to_zero(const std::vector<float4> &shade);
 double busy_ms(const spt_ctx *ctx);
 int collect_timings(spt_ctx *ctx, bool wait = true);
 EventPair get_pair(spt_ctx *ctx);

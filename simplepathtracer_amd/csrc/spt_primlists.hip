@@ -1,5 +1,5 @@
 // spt_primlists.hip -- the primary-ray candidate lists (PrimLists, spt_internal.h) built on
-// the device: spt_update_scene's list build (spt_update.cpp).
+// the device: spt_update_scene's list build (spt_scenestate.cpp update_lists).
 //
 // The lists are those of the host builder (spt_accel.cpp build_prim_lists): per 8x8 and 8x4
 // pixel block the slots whose member test a primary ray of the block can pass, ascending,

@@ -12,12 +12,12 @@ spt::FoldArgs fold_args(const spt_ctx *ctx, const uint32_t *samples, uint32_t sl
     spt::FoldArgs fa{};
     fa.samples = samples;
     fa.slot_words = slot_words;
-    fa.shade = ctx->d_shade;
+    fa.shade = ctx->scene.d_shade;
     for (int j = 0; j < 3; ++j) fa.sky[j] = ctx->cam.sky[j];
     fa.code_div = spt::make_fastdiv(ctx->code_stride);
     // (a table the setters left stale is not used: rebuild_ctab, render_impl)
-    fa.ctab = ctab_valid(ctx) ? ctx->d_ctab : nullptr;
-    fa.ctab_n = fa.ctab ? ctx->ctab_n : 0u;
+    fa.ctab = ctab_valid(ctx) ? ctx->scene.d_ctab : nullptr;
+    fa.ctab_n = fa.ctab ? ctx->scene.ctab_n : 0u;
     return fa;
 }
 

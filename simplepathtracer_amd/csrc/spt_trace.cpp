@@ -46,7 +46,7 @@ int trace_launch(spt_ctx *ctx, const spt::TraceArgs &a, hipStream_t s)
     spt::FoldArgs f = fold_args(ctx, nullptr, 1);
     // the colour table holds the codes of the context's depth; a call deeper than that
     // writes codes past it and decodes them arithmetically
-    if (f.ctab && a.scene.code_jmax > ctx->ctab_jmax) {
+    if (f.ctab && a.scene.code_jmax > ctx->scene.ctab_jmax) {
         f.ctab = nullptr;
         f.ctab_n = 0;
     }

@@ -229,6 +229,22 @@ def test_staging_plans_match_the_inline_layouts(tmp_path):
     assert out.returncode == 0 and out.stdout.strip() == "ok", out.stdout + out.stderr
 
 
+def test_candidate_list_plan_matches_literal_values(tmp_path):
+    """The plan of the primary-ray candidate lists (spt_primplan.h: device or host builder
+    with its reason, and bw, nb8, nb4, stride, total of the device's arrays) against literal
+    values, in tests/cpp/primplan_check.cpp: plain g++, AddressSanitizer + UBSan linked into
+    the executable."""
+    import os
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = tmp_path / "primplan_check"
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined",
+                    "-I", os.path.join(root, "simplepathtracer_amd", "csrc"),
+                    os.path.join(root, "tests", "cpp", "primplan_check.cpp"), "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and out.stdout.strip() == "ok", out.stdout + out.stderr
+
+
 @pytest.mark.parametrize("w,h", [(4, 3), (5, 2), (1, 1), (7, 6)])
 def test_save_bmp_matches_stb_layout(native, tmp_path, w, h):
     """io::SaveImage (IOHelpers.hpp:24-27) calls stbi_write_bmp(path, w, h, 3, g_data);

@@ -120,7 +120,7 @@ def check_region(ctx, region, spp, task, what, fw=FW, fh=FH):
 
 
 def halvings_to_zero(colors):
-    """code_jz (spt_ctx.cpp): halvings after which every finite albedo, times 0.5f, is 0."""
+    """code_jz (spt_scenestate.cpp): halvings after which every finite albedo, times 0.5f, is 0."""
     jz = 0
     for a in np.asarray(colors, np.float32)[:, :3].ravel():
         if not np.isfinite(a):

@@ -422,3 +422,150 @@ def test_accumulator_with_refit_returns_the_same_images(spt):
     for k, (a, b) in enumerate(zip(images[False], images[True])):
         assert np.array_equal(bits(a), bits(b)), f"frame {k}"
     assert not np.array_equal(bits(images[True][0]), bits(images[True][5]))
+
+
+# ---------------------------------------------------------------- setters and updates in turn
+
+def launched_render(c, w=W, h=H):
+    """A launched render: it builds the fold's colour table where that is stale (a batched host
+    call does not), so fold_table_entries shows whether a step left the table standing."""
+    import torch
+    d = torch.zeros((w * h, 4), dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    c.render_rows_async(0, 0, h, 1, 1, 0, 0, w, d.data_ptr(), 0)
+    c.synchronize()
+
+
+def visible(c):
+    st = c.stats()
+    return (st["prim_list_builds"], st["prim_list_blocks"], st["prim_list_entries"], st["fold_table_entries"])
+
+
+# (prim_list_builds, prim_list_blocks, prim_list_entries, fold_table_entries) after each step of
+# cases 1-3, as the commit before the scene state had one owner gave them for these sequences
+# (this test's body run against that commit's library on an MI355X); they pin that a refit
+# leaves the colour table standing, that a setter rebuilds lists only when their key changed,
+# and which builder (packed host runs, fixed-stride device runs) filled the counters
+STEPS = {
+    "params": [(1, 41, 588, 1312), (2, 48, 728, 1312), (3, 57, 1052, 1312), (3, 57, 1052, 1312)],
+    "tree": [(2, 48, 728, 1312), (3, 48, 728, 0), (3, 48, 728, 1280), (4, 48, 756, 1280)],
+    "camera": [(2, 48, 728, 1312), (2, 48, 728, 1312), (3, 41, 588, 1312)],
+}
+
+
+def same_as_fresh(spt, upd, scene, camera, what, frame=(W, H, SPP), tree=None, rays_of=None):
+    fresh = make_ctx(spt, scene, camera, frame, tree)
+    try:
+        rays = rays_for(scene if rays_of is None else rays_of)
+        assert_same(outputs(upd, rays, frame), outputs(fresh, rays, frame), what)
+    finally:
+        fresh.close()
+
+
+def interleave_params(spt, a, b, cam0, cam1, seen):
+    upd = make_ctx(spt, a, cam0)
+    try:
+        launched_render(upd)
+        seen.append(visible(upd))
+        upd.update_scene(b.centers, *cam1)
+        seen.append(visible(upd))
+        upd.set_params(64, 64, SPP, DEPTH, SEED)
+        seen.append(visible(upd))
+        same_as_fresh(spt, upd, b, cam1, "update, then set_params", frame=(64, 64, SPP), rays_of=a)
+        seen.append(visible(upd))
+    finally:
+        upd.close()
+
+
+def interleave_tree(spt, a, b, cam0, cam1, seen):
+    upd = make_ctx(spt, a, cam0)
+    try:
+        launched_render(upd)
+        upd.update_scene(b.centers, *cam1)
+        seen.append(visible(upd))
+        upd.set_cluster_tree(0)  # rebuilds from the context's host copy of the centres: the moved ones
+        seen.append(visible(upd))
+        same_as_fresh(spt, upd, b, cam1, "update, then set_cluster_tree(0)", tree=0, rays_of=a)
+        launched_render(upd)
+        seen.append(visible(upd))
+        info = upd.update_scene(a.centers)
+        assert info["refit"] == 1
+        seen.append(visible(upd))
+        same_as_fresh(spt, upd, a, cam1, "then update on the flat list", tree=0, rays_of=a)
+    finally:
+        upd.close()
+
+
+def interleave_camera(spt, a, b, cam0, cam1, seen):
+    upd = make_ctx(spt, a, cam0)
+    try:
+        launched_render(upd)
+        info = upd.update_scene(b.centers, *cam1)
+        assert info["lists_on_device"] == 1
+        seen.append(visible(upd))
+        before = upd.prim_lists(0)
+        upd.set_camera(cam1[0], cam1[1], SKY)  # the values the update gave: the key stands
+        seen.append(visible(upd))
+        assert seen[-1][0] == seen[-2][0], "set_camera with the update's own camera built lists"
+        for x, y in zip(upd.prim_lists(0), before):
+            assert np.array_equal(x, y)
+        upd.set_camera(cam0[0], cam0[1], SKY)
+        seen.append(visible(upd))
+        assert seen[-1][0] == seen[-2][0] + 1
+        dev, host = upd.prim_lists(0), upd.prim_lists(1)
+        assert dev[4] and host[4]
+        for x, y in zip(dev, host):  # a setter's lists are the host builder's packed runs
+            assert np.array_equal(x, y)
+        same_as_fresh(spt, upd, b, cam0, "update, then set_camera", rays_of=a)
+    finally:
+        upd.close()
+
+
+def interleave_sphere_count(spt, a, b, cam0, cam1, seen):
+    upd = make_ctx(spt, a, cam0)
+    try:
+        upd.update_scene(b.centers)
+        small = spt.cornell3()
+        upd.set_scene(small)
+        moved = moved_scene(spt, small, moves(small)["jitter"])
+        info = upd.update_scene(moved.centers)
+        assert info["refit"] == 1
+        same_as_fresh(spt, upd, moved, cam0, "update, set_scene of 4 spheres, update")
+    finally:
+        upd.close()
+
+
+def interleave_fallback(spt, a, b, cam0, cam1, seen, monkeypatch):
+    monkeypatch.setenv("SPT_PRIM_DEVICE_SLOTS", "64")  # generate_spheres(1) has 164 slots
+    host = make_ctx(spt, a, cam0)
+    monkeypatch.delenv("SPT_PRIM_DEVICE_SLOTS")
+    dev = make_ctx(spt, a, cam0)
+    try:
+        ih, idv = host.update_scene(b.centers, *cam1), dev.update_scene(b.centers, *cam1)
+        assert (ih["lists_on_device"], ih["lists_reason"]) == (0, "slots")
+        assert (idv["lists_on_device"], idv["lists_reason"]) == (1, "device")
+        rays = rays_for(a)
+        assert_same(outputs(host, rays), outputs(dev, rays), "host fallback against the device builder")
+    finally:
+        host.close()
+        dev.close()
+
+
+@pytest.mark.parametrize("case", ("params", "tree", "camera", "sphere_count", "fallback"))
+def test_setters_and_updates_interleave(spt, monkeypatch, case):
+    """Setters and spt_update_scene in turn on one context leave the state a fresh context
+    given the same final state has; the counters spt_stats shows after every step of the
+    first three sequences are the ones recorded in STEPS."""
+    a = spt.generate_spheres(1)
+    b = moved_scene(spt, a, moves(a)["jitter"])
+    cam0, cam1 = cam(spt, EYE0, LOOK0), cam(spt, EYE1, LOOK1)
+    seen = []
+    body = {"params": interleave_params, "tree": interleave_tree, "camera": interleave_camera,
+            "sphere_count": interleave_sphere_count}.get(case)
+    if body is None:
+        interleave_fallback(spt, a, b, cam0, cam1, seen, monkeypatch)
+    else:
+        body(spt, a, b, cam0, cam1, seen)
+    print(f"interleave {case}: {seen}")
+    if case in STEPS:
+        assert seen == STEPS[case]
