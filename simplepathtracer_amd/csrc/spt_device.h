@@ -97,14 +97,41 @@ __device__ __forceinline__ float div_rn(float a, float b)
 // Math.hpp:140-154: v / sqrt(|v|^2), lane-wise IEEE division.  Components in
 // [2^-40, 2^40] give |v|^2 in [2^-80, 2^82) (unscaled sqrt path) and a divisor in
 // [2^-40, 2^41], inside div_core's range; other lanes take the full sequences.
+//
+// The range test of all three components is one predicate and the full sequences sit
+// behind one wave-uniform branch, so the short path is straight-line code: written as
+// `if (!(ok(x) && ok(y) && ok(z)))` the compiler nested the short path three deep under
+// the components' tests (six compares, two saveexec regions and 14 mask merges around 27
+// VALU).
+//
+// The predicate, ok3(a, L) = min3|a| >= 2^-40 && max3|a| <= 2^40 && L <= 2^82, equals
+// div_operand_ok(a.x) && div_operand_ok(a.y) && div_operand_ok(a.z) for every input
+// (tests/cpp/normalize_guard_check.cpp).  v_min3_f32 / v_max3_f32 drop a
+// NaN operand, so the two range compares alone would pass a NaN component; L = lensq(a)
+// is NaN whenever a component is, and `L <= 2^82` is false then and true whenever the
+// three components are in range (L <= 3 * 2^80 (1 + 2^-23)^2).
+// Returned as the wave mask of the lanes that are NOT ok, each compare balloted by itself
+// (the ballot of a combined predicate goes through a VGPR and back).
+__device__ __forceinline__ unsigned long long normalize_slow_mask(f3 a, float L)
+{
+    float lo, hi;
+    asm("v_min3_f32 %0, |%1|, |%2|, |%3|" : "=v"(lo) : "v"(a.x), "v"(a.y), "v"(a.z));
+    asm("v_max3_f32 %0, |%1|, |%2|, |%3|" : "=v"(hi) : "v"(a.x), "v"(a.y), "v"(a.z));
+    return __ballot(!(lo >= 0x1p-40f)) | __ballot(!(hi <= 0x1p40f)) | __ballot(!(L <= 0x1p82f));
+}
 __device__ __forceinline__ f3 normalize(f3 a)
 {
     const float L = lensq(a);
     const Recip r = recip(sqrt_pos_normal(L));
     f3 out = f3{div_core(a.x, r), div_core(a.y, r), div_core(a.z, r)};
-    if (__builtin_expect(!(div_operand_ok(a.x) && div_operand_ok(a.y) && div_operand_ok(a.z)), 0)) {
+    const unsigned long long slow = normalize_slow_mask(a, L);
+    if (__builtin_expect(slow != 0ull, 0)) {
+        // some lane of the wave is out of range: the full sequences, kept by those lanes only
+        const bool mine = __builtin_amdgcn_inverse_ballot_w64(slow);
         const float l = __builtin_sqrtf(L);
-        out = f3{a.x / l, a.y / l, a.z / l};
+        out.x = mine ? a.x / l : out.x;
+        out.y = mine ? a.y / l : out.y;
+        out.z = mine ? a.z / l : out.z;
     }
     return out;
 }

@@ -112,7 +112,7 @@ struct DealTable {
         for (uint32_t np = 0; np <= 64u; ++np) e[np] = make_deal_rule(np);
     }
 };
-static constexpr DealTable kDealTable{};
+alignas(16) static constexpr DealTable kDealTable{};  // a rule is one 16-byte scalar load
 // first lane and lane count of pending rank `rank` (< np)
 __host__ __device__ inline uint32_t deal_start(const DealRule &r, uint32_t rank)
 {

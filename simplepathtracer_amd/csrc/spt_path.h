@@ -1082,8 +1082,11 @@ struct Path {
 // the trial base jb is common.  Either way a lane's trials are evaluated in whole
 // prefixes, so the result and the advanced state st0 + 3 (j* + 1) gamma equal the
 // sequential loop's.  Must be called in wave-uniform control flow, all 64 lanes active.
-// `lds`: 64 words of wave-private LDS.
-__device__ __forceinline__ f3 coop_ball_vector(uint64_t &st, bool need, uint32_t *lds, unsigned long long *rounds = nullptr)
+// `needm`: the wave mask of the lanes that need a vector.  `lds`: 64 words of wave-private
+// LDS.  The pending lanes travel as a wave mask from ballot to ballot (a ballot of a
+// compare is the compare's own result; a ballot of a combined lane predicate is a
+// v_cndmask 0, 1 / v_cmp_ne 0 pair).
+__device__ __forceinline__ f3 coop_ball_vector(uint64_t &st, unsigned long long needm, uint32_t *lds, unsigned long long *rounds = nullptr)
 {
     const uint32_t lane = __lane_id();
     const uint64_t st0 = st;
@@ -1091,7 +1094,6 @@ __device__ __forceinline__ f3 coop_ball_vector(uint64_t &st, bool need, uint32_t
     uint32_t jacc = 0;
     unsigned long long pend;
     uint32_t jb;
-    const unsigned long long needm = __ballot(need);
     if (SPT_SAMPLER_SKIP0 && __popcll(needm) <= 32) {
         // at most 32 lanes need a vector: every one gets two or more helpers from trial 0 on
         // (round 0 would run one trial per lane for all 64, half of them for nothing)
@@ -1103,7 +1105,7 @@ __device__ __forceinline__ f3 coop_ball_vector(uint64_t &st, bool need, uint32_t
         r.x = uniform(t, -0.5f, 0.5f);
         r.y = uniform(t, -0.5f, 0.5f);
         r.z = uniform(t, -0.5f, 0.5f);
-        pend = __ballot(need && lensq(r) < 0.25f);
+        pend = needm & __ballot(lensq(r) < 0.25f);
         jb = 1;
     }
     const uint32_t s_lo = (uint32_t)st0, s_hi = (uint32_t)(st0 >> 32);
@@ -1115,9 +1117,16 @@ __device__ __forceinline__ f3 coop_ball_vector(uint64_t &st, bool need, uint32_t
     // jacc of a pending lane: its trials done so far (the next one's index), then its
     // accepted trial's index; it travels to the helpers beside the lane id
     if (jb != 0u) jacc = __builtin_amdgcn_inverse_ballot_w64(pend) ? 1u : 0u;
+    // the table's address is formed once, ahead of the rounds (the compiler re-formed it
+    // from the program counter in every round, twice), and a rule is one 16-byte load
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    typedef __attribute__((address_space(4))) const u32x4 cu32x4;
+    cu32x4 *deal = (cu32x4 *)&kDealTable.e[0];
+    asm volatile("" : "+s"(deal));
     while (pend != 0ull) {
         if (SPT_DIAG && rounds) rounds[1] += 1;  // cooperative rounds after round 0
-        const DealRule dr = kDealTable.e[__popcll(pend)];  // wave-uniform: one scalar load
+        const u32x4 dw = deal[__popcll(pend)];  // wave-uniform: one scalar load
+        const DealRule dr{((uint64_t)dw.y << 32) | dw.x, dw.z, dw.w};
         const bool is_p = __builtin_amdgcn_inverse_ballot_w64(pend);
         const uint32_t rank = lane_rank(pend);
         if (is_p) lds[rank] = (jacc << 6) | lane;
@@ -1136,12 +1145,13 @@ __device__ __forceinline__ f3 coop_ball_vector(uint64_t &st, bool need, uint32_t
         const uint32_t start = deal_start(dr, rank), cnt = deal_count(dr, rank);
         const unsigned long long seg = acc >> (start & 63u);
         const uint32_t tstar = seg != 0ull ? (uint32_t)__builtin_ctzll(seg) : 64u;
-        const bool found = is_p && tstar < cnt;
+        const unsigned long long foundm = pend & __ballot(tstar < cnt);
+        const bool found = __builtin_amdgcn_inverse_ballot_w64(foundm);
         const uint32_t from = found ? start + tstar : lane;
         const float rx = __shfl(c.x, (int)from), ry = __shfl(c.y, (int)from), rz = __shfl(c.z, (int)from);
         if (found) r = mk(rx, ry, rz);
         if (is_p) jacc += tstar < cnt ? tstar : cnt;
-        pend = __ballot(is_p && !found);
+        pend &= ~foundm;
     }
 #else
     while (pend != 0ull) {
@@ -1178,7 +1188,7 @@ __device__ __forceinline__ f3 coop_ball_vector(uint64_t &st, bool need, uint32_t
         jb += 1u << lg;
     }
 #endif
-    if (need) st = st0 + (uint64_t)(3u * (jacc + 1u)) * kGamma;
+    if (__builtin_amdgcn_inverse_ballot_w64(needm)) st = st0 + (uint64_t)(3u * (jacc + 1u)) * kGamma;
 #if SPT_DIAG
     if (rounds) rounds[2] += __builtin_amdgcn_s_memtime() - t_in;  // sampler cycles
 #endif
@@ -1322,14 +1332,39 @@ __device__ __forceinline__ void refract_event(const float4 *__restrict__ slots, 
 // WT (the render service): the sample word is stored write-through (sc1: it leaves the
 // XCD's L2 at once), so the completion count that follows needs only the wave's own
 // s_waitcnt, not an L2 write-back (spt_kernels.hip svc_flush).
+//
+// The step's outcomes arrive as wave masks (shade_step_body).  `mode` is wave-uniform: one
+// branch on it, so that segment mode runs none of the task mode's key bookkeeping; the
+// segment arm is straight-line up to the finishing lanes' store.
 template <bool WT = false>
-__device__ __forceinline__ void finish_step(uint32_t mode, uint32_t *samples, Path &ps, bool fin, bool spec_event,
-                                            bool refr_event, bool sky, uint32_t word, unsigned long long &done,
-                                            unsigned long long &dropped)
+__device__ __forceinline__ void finish_step(uint32_t mode, uint32_t *samples, Path &ps, unsigned long long finm,
+                                            unsigned long long specm, unsigned long long refrm, unsigned long long skym,
+                                            uint32_t word, unsigned long long &done, unsigned long long &dropped)
 {
+    typedef __attribute__((address_space(1))) uint32_t gu32_t;
+    typedef __attribute__((address_space(1))) unsigned long long gu64_t;
+    const uint32_t k = ps.spec & 0xFFFFu;
+    const bool spec_event = __builtin_amdgcn_inverse_ballot_w64(specm);
+    if (mode == 0u) {
+        ps.spec += spec_event ? 1u : 0u;
+        const unsigned long long capm = specm & __ballot(k + 1u > kSpecularCap);
+        word = __builtin_amdgcn_inverse_ballot_w64(capm) ? kZeroWord : word;
+        if (__builtin_amdgcn_inverse_ballot_w64(finm | capm)) {
+            // RenderSegment counts every sample: one word per slot
+            if (WT)
+                __hip_atomic_store((gu32_t *)(samples + ps.item), word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else
+                samples[ps.item] = word;
+            ps.phase = PH_IDLE;
+            ps.d = mk(0.f, 0.f, 0.f);
+            ++done;
+        }
+        return;
+    }
+    bool fin = __builtin_amdgcn_inverse_ballot_w64(finm);
+    const bool refr_event = __builtin_amdgcn_inverse_ballot_w64(refrm), sky = __builtin_amdgcn_inverse_ballot_w64(skym);
     bool counted = true;
     if (spec_event) {
-        const uint32_t k = ps.spec & 0xFFFFu;
         if (mode == 1u && k < kTaskPasses && refr_event) ps.spec |= 1u << (16u + k);
         ++ps.spec;
         if (mode == 1u && k + 1u >= kTaskPasses) {
@@ -1344,23 +1379,13 @@ __device__ __forceinline__ void finish_step(uint32_t mode, uint32_t *samples, Pa
         }
     }
     if (fin) {
-        typedef __attribute__((address_space(1))) uint32_t gu32_t;
-        typedef __attribute__((address_space(1))) unsigned long long gu64_t;
-        if (mode == 0u) {
-            // RenderSegment counts every sample: one word per slot
-            if (WT)
-                __hip_atomic_store((gu32_t *)(samples + ps.item), word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            else
-                samples[ps.item] = word;
-        } else {
-            const uint32_t key =
-                counted ? 1u + (((ps.spec & 0xFFFFu) << 11) | (sky ? 1u << 10 : 0u) | ((ps.spec >> 16) & 0x3FFu)) : 0u;
-            if (WT)
-                __hip_atomic_store((gu64_t *)(samples + (size_t)2 * ps.item), (unsigned long long)word | ((unsigned long long)key << 32),
-                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            else
-                *(uint2 *)(samples + (size_t)2 * ps.item) = make_uint2(word, key);
-        }
+        const uint32_t key =
+            counted ? 1u + (((ps.spec & 0xFFFFu) << 11) | (sky ? 1u << 10 : 0u) | ((ps.spec >> 16) & 0x3FFu)) : 0u;
+        if (WT)
+            __hip_atomic_store((gu64_t *)(samples + (size_t)2 * ps.item), (unsigned long long)word | ((unsigned long long)key << 32),
+                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else
+            *(uint2 *)(samples + (size_t)2 * ps.item) = make_uint2(word, key);
         ps.phase = PH_IDLE;
         ps.d = mk(0.f, 0.f, 0.f);
         ++done;
@@ -1372,6 +1397,13 @@ __device__ __forceinline__ void finish_step(uint32_t mode, uint32_t *samples, Pa
 // bounce loop (21-37) in PH_DLOOP.  Finishing paths write their sample slot.
 // Called by every lane of the wave (`act` = the lane holds a path), so the
 // cooperative cube-minus-ball sampler runs in uniform control flow.
+//
+// The step's decisions are wave masks, each the ballot of one compare joined on the scalar
+// unit, and a lane's values are chosen by selects: written as a chain of `if`s over
+// `act`, `dl` and `m` the compiler nested three exec regions and merged the flags with
+// some thirty scalar mask instructions.  Two exec regions remain,
+// the scatter arithmetic and the refraction event, each lane's arithmetic and its order
+// unchanged.
 template <bool KARG, bool WT, bool SAMPLER>
 __device__ __forceinline__ void shade_step_body(const RenderArgs &a, Path &ps, const Hit &h, bool act,
                                                 unsigned long long &done, unsigned long long &dropped, uint32_t *lds,
@@ -1398,50 +1430,44 @@ __device__ __forceinline__ void shade_step_body(const RenderArgs &a, Path &ps, c
         code_jmax = k.scene.code_jmax;
     }
     const uint32_t idx = h.idx;
-    bool fin = false;
-    uint32_t word = kZeroWord;  // the sample's code (spt_internal.h code_word)
-    const bool dl = ps.phase == PH_DLOOP;
+    const unsigned long long actm = __ballot(act);
+    const unsigned long long hitm = actm & __ballot(idx != kMiss);
     uint32_t m = SPT_SKYBOX_ID;
-    if (act && idx != kMiss) m = mat[idx];
-    bool scatter = false, refr = false;
-    if (!act) {
-    } else if (dl) {
-        // while (--bounceCount && sphereIndex < N), SingleThreadPathTracer.hpp:28
-        --ps.bounce;
-        const bool end = ps.bounce == 0u || idx == kMiss;
-        if (end) {
-            // the albedo of the first diffuse hit halved 1 + j times: once at that hit
-            // (line 24) and once per further bounce (line 31), j = bounces - bounce - 1
-            // (saturated where every albedo of the scene is 0: diffuse_code)
-            const uint32_t j = min(bounces - ps.bounce - 1u, code_jmax);
-            word = code_word(diffuse_code(j, ps.slot, code_stride));
-            fin = true;
-        }
-        scatter = !end;
-        refr = false;
-    } else {
-        // TraceAndSampleColor material switch, SingleThreadPathTracer.hpp:98-111
-        scatter = m == SPT_DIFFUSE_ID || m == SPT_REFLECTIVE_ID;
-        refr = m == SPT_REFRACTIVE_ID;
-        if (!scatter && !refr) {
-            // SampleColorSkybox, lines 11-14: initColor * (d.y + 1) * 0.5, rebuilt by the
-            // fold from k = d.y + 1
-            word = __float_as_uint(ps.d.y + 1.f);
-            fin = true;
-        }
-    }
-    bool spec_event = false;
+    if (__builtin_amdgcn_inverse_ballot_w64(hitm)) m = mat[idx];
+    // the diffuse loop: while (--bounceCount && sphereIndex < N), SingleThreadPathTracer.hpp:28
+    const unsigned long long dlm = actm & __ballot(ps.phase == PH_DLOOP);
+    const bool dl = __builtin_amdgcn_inverse_ballot_w64(dlm);
+    const uint32_t nb = ps.bounce - 1u;
+    ps.bounce = dl ? nb : ps.bounce;
+    const unsigned long long endm = dlm & (__ballot(nb == 0u) | ~hitm);
+    // TraceAndSampleColor material switch, SingleThreadPathTracer.hpp:98-111
+    const unsigned long long trm = actm & ~dlm;
+    const unsigned long long diffm = trm & __ballot(m == SPT_DIFFUSE_ID);
+    const unsigned long long mirm = trm & __ballot(m == SPT_REFLECTIVE_ID);
+    const unsigned long long refrm = trm & __ballot(m == SPT_REFRACTIVE_ID);
+    const unsigned long long skym = trm & ~(diffm | mirm | refrm);
+    const unsigned long long scatm = (dlm & ~endm) | diffm | mirm;
+    // the sample's code (spt_internal.h code_word).  A loop's end: the albedo of the first
+    // diffuse hit halved 1 + j times: once at that hit (line 24) and once per further bounce
+    // (line 31), j = bounces - bounce - 1 (saturated where every albedo of the scene is 0:
+    // diffuse_code).  SampleColorSkybox, lines 11-14: initColor * (d.y + 1) * 0.5, rebuilt by
+    // the fold from k = d.y + 1
+    const uint32_t j = min(bounces - nb - 1u, code_jmax);
+    uint32_t word = kZeroWord;
+    word = __builtin_amdgcn_inverse_ballot_w64(endm) ? code_word(diffuse_code(j, ps.slot, code_stride)) : word;
+    word = __builtin_amdgcn_inverse_ballot_w64(skym) ? __float_as_uint(ps.d.y + 1.f) : word;
     // (SAMPLER = false: SPT_DUP attribution's copy of the step, without the sampler)
-    const f3 rv_coop = SAMPLER ? coop_ball_vector(ps.st, scatter, lds, diag_rounds) : opaque_v3(mk(0.1f, 0.2f, 0.3f));
+    const f3 rv_coop = SAMPLER ? coop_ball_vector(ps.st, scatm, lds, diag_rounds) : opaque_v3(mk(0.1f, 0.2f, 0.3f));
     if ((SPT_DUP & 2) && SAMPLER) {
         uint64_t st2 = opaque_v(ps.st);
-        const f3 r2 = coop_ball_vector(st2, opaque_v(scatter ? 1u : 0u) != 0u, lds);
+        const bool scatter = __builtin_amdgcn_inverse_ballot_w64(scatm);
+        const f3 r2 = coop_ball_vector(st2, __ballot(opaque_v(scatter ? 1u : 0u) != 0u), lds);
         sink_v(r2.x);
         sink_v(r2.y);
         sink_v(r2.z);
         sink_v(st2);
     }
-    if (scatter) {
+    if (__builtin_amdgcn_inverse_ballot_w64(scatm)) {
         // contact point + normal + cube-minus-ball vector, shared by the diffuse
         // first hit (lines 23-26), the diffuse loop (30-33) and the mirror (41-43)
         const float4 cs = hit[idx];
@@ -1449,21 +1475,20 @@ __device__ __forceinline__ void shade_step_body(const RenderArgs &a, Path &ps, c
         ps.o = contact(ps.o, ps.d, h.t);
         const f3 nrm = normalize(sub(ps.o, C));
         f3 rv = rv_coop;
-        f3 base;
-        if (dl) {
-            base = add(ps.o, nrm);  // origin + normal (+ rv), line 32; colour *= 0.5 (line 31) in the code
-        } else if (m == SPT_DIFFUSE_ID) {
-            ps.slot = idx;  // colour = albedo * 0.5 (line 24), in the code
-            base = nrm;
-            ps.phase = PH_DLOOP;
-        } else {
+        // the loop: origin + normal (+ rv), line 32, colour *= 0.5 (line 31) in the code;
+        // the first diffuse hit: the normal, colour = albedo * 0.5 (line 24) in the code
+        const f3 on = add(ps.o, nrm);
+        f3 base = mk(dl ? on.x : nrm.x, dl ? on.y : nrm.y, dl ? on.z : nrm.z);
+        if (__builtin_amdgcn_inverse_ballot_w64(mirm)) {
             base = reflect(ps.d, nrm);
             rv = mul(rv, shade[idx].w);
-            spec_event = true;
         }
         ps.d = normalize(add(base, rv));
     }
-    if (refr) {
+    const bool first = __builtin_amdgcn_inverse_ballot_w64(diffm);
+    ps.slot = first ? idx : ps.slot;
+    ps.phase = first ? PH_DLOOP : ps.phase;
+    if (__builtin_amdgcn_inverse_ballot_w64(refrm)) {
         ps.o = contact(ps.o, ps.d, h.t);
         if (SPT_DUP & 256) {
             Path p2 = ps;
@@ -1474,9 +1499,8 @@ __device__ __forceinline__ void shade_step_body(const RenderArgs &a, Path &ps, c
             sink_v(p2.st);
         }
         refract_event(hit, ps, idx);
-        spec_event = true;
     }
-    finish_step<WT>(mode, samples, ps, fin, spec_event, refr, !dl, word, done, dropped);
+    finish_step<WT>(mode, samples, ps, endm | skym, mirm | refrm, refrm, trm, word, done, dropped);
 }
 template <bool KARG = false, bool WT = false>
 __device__ __forceinline__ void shade_step(const RenderArgs &a, Path &ps, const Hit &h, bool act,
