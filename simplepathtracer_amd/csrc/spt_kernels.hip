@@ -73,8 +73,8 @@ constexpr uint32_t kLdsBlock = SPT_LDS_BLOCK;
 #define SPT_LANE_WALK 1
 #endif
 // 1: the wave-walk kernels start paths in primary batches (render_body, PRIM): 64 new
-// paths at a time, all 64 lanes, cast and shaded once together, the survivors parked
-// in a per-wave LDS queue that refills idle lanes
+// paths at a time, all 64 lanes, cast and shaded once together, the paths the lanes held
+// before parked in a per-wave LDS queue that refills idle lanes
 #ifndef SPT_PRIM
 #define SPT_PRIM 1
 #endif
@@ -87,6 +87,8 @@ constexpr uint32_t kLdsBlock = SPT_LDS_BLOCK;
 // A path parked in LDS (the primary queue of render_body): 12 words, structure of arrays
 // over the wave's 64 rows (conflict-free b32 accesses).  Fields: item, st (2), o (3), d (3),
 // slot, bounce, phase | spec << 2; the render service adds its job's counter (word 12).
+// Only live paths are parked, into rows [0, n) by rank when a batch starts, and each is
+// popped once by an idle lane (render_body's refill).
 constexpr uint32_t kParkWords = 12;
 template <bool JOB = false>
 __device__ __forceinline__ void park_path(uint32_t *q, int32_t row, const Path &ps)
@@ -536,21 +538,25 @@ __device__ __forceinline__ void render_body(const RenderArgs &a)
     // the LDS copy holds byte-offset skip links when only lane_cast walks it
     constexpr bool LDS_BYTES = LDSN && SPT_LANE_WALK && SPT_LANE_BUDGET > 0;
     // Primary batches (SPT_PRIM; the wave-walk kernels): when idle lanes want
-    // more paths than the wave's queue holds, every lane parks its own path in the queue
-    // rows, takes a NEW item (64 consecutive items: one sample of one 8x8 tile) and the
-    // wave runs one ordinary iteration -- cast + shading step -- over those 64 primary
-    // rays; then each lane takes its own path back and the survivors (paths not finished
-    // by their first shading step) fill the queue, from which idle lanes are refilled.
+    // more paths than the wave's queue holds (it is empty then), the live lanes park their
+    // own paths in the queue, compacted by rank, every lane takes a NEW item (64
+    // consecutive items: one sample of one 8x8 tile) and the wave runs one ordinary
+    // iteration -- cast + shading step -- over those 64 primary rays.  The survivors
+    // (paths not finished by their first shading step) stay in their lanes, in pixel
+    // order; the lanes whose path finished are idle, and the ordinary refill pops the
+    // queued own paths into them.  A path is written to LDS once and read once per batch
+    // it sits out, and the loop carries one Path.
     // The primary cast is one coherent bundle from the eye (the wave walk's union of
     // leaves is about a single ray's), and every path enters the main loop one cast in.
     // Per path the arithmetic and its order are unchanged: bit-identical frames.
     constexpr bool PRIM = SPT_PRIM && !LDSN && !GLANE;
     constexpr uint32_t PW = kParkWords + (SVC ? 1u : 0u);  // parked words per path
     __shared__ uint32_t s_park[PRIM ? (BLOCK / 64u) * PW * 64u : 1];
-    // the lane's own row of the wave's rows; row r is addressed from it as r - lane, so that
-    // the rows' base is not a second register live for the whole kernel (it went to scratch)
-    uint32_t *const park = s_park + (PRIM ? opaque_v((threadIdx.x >> 6) * PW * 64u + lane) : 0u);
-    auto prow = [&](uint32_t r) -> int32_t { return (int32_t)r - (int32_t)lane; };
+    // the wave's rows: only a refill touches them, so their base is a scalar (wave-uniform)
+    // and not a vector register live for the whole kernel (as a lane's row address it went to
+    // scratch in the service's kernel once the batch's body no longer used it)
+    const uint32_t park_base = PRIM ? __builtin_amdgcn_readfirstlane(threadIdx.x & ~63u) * PW : 0u;
+    auto park_rows = [&]() -> uint32_t * { return s_park + park_base; };
     // SVC: the wave's copy of its current job's record (svc_find_job, words 0-23) and its
     // claim state (words kSvcSt..31: kept in LDS, not SGPRs, since only claims read them)
     __shared__ uint32_t s_rec[SVC ? (BLOCK / 64u) * kSvcRecWords : 1];
@@ -601,7 +607,11 @@ __device__ __forceinline__ void render_body(const RenderArgs &a)
     bool exhausted = false;  // SVC: no published claim right now (the reservation waits)
     // SVC: the wave's finished samples not yet added to completion counter acc_idx
     uint32_t acc_idx = 0, acc_cnt = 0;
-    unsigned long long casts = 0, done = 0, dropped = 0;
+    // the wave's counts: rays cast; finished samples and dropped paths, taken from the
+    // finishing masks (finish_step) in 32 bits, which hold a wave's share of a launch's or a
+    // job's items (add_counts moves them to the launch's counters)
+    unsigned long long casts = 0;
+    uint32_t done = 0, dropped = 0;
     struct {
         unsigned long long iters = 0, cast = 0, shade = 0, refill = 0;  // SPT_DIAG counts and s_memtime split
         // the primary batches' share: iterations, nodes, spheres, update branches, cast cycles
@@ -716,6 +726,18 @@ __device__ __forceinline__ void render_body(const RenderArgs &a)
         }
     };
 
+    // the wave's counts into the launch's counters: one atomic per counter and wave
+    // (same-address atomics from every lane cost a launch ~10%; see render_grid)
+    auto add_counts = [&]() {
+        if (lane == 0) {
+            if (casts) atomicAdd(&a.counters[0], casts);
+            if (done) atomicAdd(&a.counters[1], (unsigned long long)done);
+            if (dropped) atomicAdd(&a.counters[2], (unsigned long long)dropped);
+        }
+        casts = 0;
+        done = dropped = 0;
+    };
+
     for (;;) {
         // ---- refill: hand out (pixel, sample) items to idle lanes (ballot + prefix)
         // idle lanes wait until SPT_REFILL_MIN of them (or the whole wave) can be
@@ -730,7 +752,8 @@ __device__ __forceinline__ void render_body(const RenderArgs &a)
                 const uint32_t cnt = (uint32_t)__popcll(need);
                 const uint32_t rank = lane_rank(need);
                 const uint32_t take = min(cnt, q_n - q_pos);
-                if (ps.phase == PH_IDLE && rank < take) unpark_path<SVC>(park, prow(q_pos + rank), ps);
+                uint32_t *const park = park_rows();
+                if (ps.phase == PH_IDLE && rank < take) unpark_path<SVC>(park, (int32_t)(q_pos + rank), ps);
                 q_pos += take;
                 bool more = !exhausted;
                 if (SVC && cnt > take) {
@@ -738,10 +761,17 @@ __device__ __forceinline__ void render_body(const RenderArgs &a)
                     more = blk_cur < blk_end;
                 }
                 if (cnt > take && more) {
-                    // the queue is empty: park every lane's own path in its own row and
-                    // start 64 new paths (wave-uniform)
-                    park_path<SVC>(park, 0, ps);
-                    // the own path lives in LDS across the batch, not in registers
+                    // the queue is empty: the live lanes' own paths go into rows [0, n_own),
+                    // by rank, and 64 new paths start (wave-uniform).  A lane writes row
+                    // rank <= lane after the pops above have read theirs: LDS operations of
+                    // a wave complete in order.  (Where the pops took the queue's last
+                    // paths, 0 < take < cnt, those go straight back here: a round trip that
+                    // skipping the pop would save; known, not measured)
+                    const unsigned long long ownm = __ballot(ps.phase != PH_IDLE);
+                    if (ps.phase != PH_IDLE) park_path<SVC>(park, (int32_t)lane_rank(ownm), ps);
+                    q_pos = 0;
+                    q_n = (uint32_t)__popcll(ownm);
+                    // the own path lives in LDS from here on, not in registers
                     asm volatile("" ::: "memory");
                     ps.phase = PH_IDLE;
                     if (SVC) {
@@ -807,12 +837,8 @@ __device__ __forceinline__ void render_body(const RenderArgs &a)
         }
         const unsigned long long live = __ballot(ps.phase != PH_IDLE);
         if (live == 0ull) {
-            if (PRIM && prim_iter) {
-                // no item was left for the batch: the lanes' own paths back
-                unpark_path<SVC>(park, 0, ps);
-                q_n = q_pos = 0;
-                continue;
-            }
+            // (PRIM, no item was left for a batch: the own paths it queued come back
+            // through the next iteration's pop)
             if (SVC && q_pos == q_n) {
                 // no path and no published claim: publish the finished samples, then wait
                 // for a publication or the stop flag (read before the last look at the
@@ -821,6 +847,7 @@ __device__ __forceinline__ void render_body(const RenderArgs &a)
                 // host (spt_internal.h kSvcIdleTicks), then the watchdog word tells the host.
                 svc_flush(acc_idx, acc_cnt, lane);
                 acc_cnt = 0;
+                add_counts();  // a session can outlast 2^32 samples a wave: per idle spell and job
                 unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
                 bool leave = false;
                 bool closing = false;  // this wave has raised the closing flag
@@ -984,6 +1011,7 @@ __device__ __forceinline__ void render_body(const RenderArgs &a)
                 const unsigned long long m = __ballot(fin && ps.job == j);
                 if (j != acc_idx) {
                     svc_flush(acc_idx, acc_cnt, lane);
+                    add_counts();
                     acc_idx = j;
                     acc_cnt = 0;
                 }
@@ -991,19 +1019,8 @@ __device__ __forceinline__ void render_body(const RenderArgs &a)
                 fm &= ~m;
             }
         }
-        if (PRIM && prim_iter) {
-            // the lane's own path back from its row, then the batch's survivors into
-            // rows [0, n) of the queue (a lane writes row rank <= lane, after the whole
-            // wave has read its own row: LDS operations of a wave complete in order)
-            Path own;
-            unpark_path<SVC>(park, 0, own);
-            __builtin_amdgcn_wave_barrier();
-            const unsigned long long lv = __ballot(ps.phase != PH_IDLE);
-            if (ps.phase != PH_IDLE) park_path<SVC>(park, prow(lane_rank(lv)), ps);
-            ps = own;
-            q_n = (uint32_t)__popcll(lv);
-            q_pos = 0;
-        }
+        // (a primary batch ends like any iteration: its survivors stay in their lanes, in
+        // pixel order, and its finished lanes are idle for the next refill's pops)
         SPT_STAMP(dc.shade);
     }
 
@@ -1013,18 +1030,7 @@ __device__ __forceinline__ void render_body(const RenderArgs &a)
         kargs_t &k = *kernarg_args();
         if (lane == 0) __hip_atomic_fetch_add((gu32 *)(k.svc_ctl + kSvcLive), 0xFFFFFFFFu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    // per-lane done/dropped -> wave sums (butterfly), one atomic per counter and wave
-    // (same-address atomics from every lane cost a launch ~10%; see render_grid)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        done += __shfl_xor(done, o);
-        dropped += __shfl_xor(dropped, o);
-    }
-    if (lane == 0) {
-        if (casts) atomicAdd(&a.counters[0], casts);
-        if (done) atomicAdd(&a.counters[1], done);
-        if (dropped) atomicAdd(&a.counters[2], dropped);
-    }
+    add_counts();
 #if SPT_DIAG
     if (lane == 0) {
         atomicAdd(&a.counters[4], dc.iters);

@@ -1336,10 +1336,16 @@ __device__ __forceinline__ void refract_event(const float4 *__restrict__ slots, 
 // The step's outcomes arrive as wave masks (shade_step_body).  `mode` is wave-uniform: one
 // branch on it, so that segment mode runs none of the task mode's key bookkeeping; the
 // segment arm is straight-line up to the finishing lanes' store.
-template <bool WT = false>
+// `done` and `dropped` are the wave's counts, taken from the finishing masks on the scalar
+// unit: every lane of the wave holds the same value, and one lane reports it.  That holds
+// only where the whole wave reaches the call together (full exec, lane 0 among it), as in
+// render_body, wf_render's chunk loop and trace_body: called under divergence the ballots
+// see the active lanes only and the counts come out short, silently.  CNT is the caller's
+// counter type: 32 bits hold a wave's share of a launch (items are 32-bit).
+template <bool WT = false, class CNT>
 __device__ __forceinline__ void finish_step(uint32_t mode, uint32_t *samples, Path &ps, unsigned long long finm,
                                             unsigned long long specm, unsigned long long refrm, unsigned long long skym,
-                                            uint32_t word, unsigned long long &done, unsigned long long &dropped)
+                                            uint32_t word, CNT &done, CNT &dropped)
 {
     typedef __attribute__((address_space(1))) uint32_t gu32_t;
     typedef __attribute__((address_space(1))) unsigned long long gu64_t;
@@ -1349,6 +1355,7 @@ __device__ __forceinline__ void finish_step(uint32_t mode, uint32_t *samples, Pa
         ps.spec += spec_event ? 1u : 0u;
         const unsigned long long capm = specm & __ballot(k + 1u > kSpecularCap);
         word = __builtin_amdgcn_inverse_ballot_w64(capm) ? kZeroWord : word;
+        done += (CNT)__popcll(finm | capm);
         if (__builtin_amdgcn_inverse_ballot_w64(finm | capm)) {
             // RenderSegment counts every sample: one word per slot
             if (WT)
@@ -1357,7 +1364,6 @@ __device__ __forceinline__ void finish_step(uint32_t mode, uint32_t *samples, Pa
                 samples[ps.item] = word;
             ps.phase = PH_IDLE;
             ps.d = mk(0.f, 0.f, 0.f);
-            ++done;
         }
         return;
     }
@@ -1372,12 +1378,13 @@ __device__ __forceinline__ void finish_step(uint32_t mode, uint32_t *samples, Pa
             fin = true;
             counted = false;
             word = kZeroWord;
-            ++dropped;
         } else if (k + 1u > kSpecularCap) {
             fin = true;
             word = kZeroWord;
         }
     }
+    dropped += (CNT)__popcll(__ballot(!counted));
+    done += (CNT)__popcll(__ballot(fin));
     if (fin) {
         const uint32_t key =
             counted ? 1u + (((ps.spec & 0xFFFFu) << 11) | (sky ? 1u << 10 : 0u) | ((ps.spec >> 16) & 0x3FFu)) : 0u;
@@ -1388,7 +1395,6 @@ __device__ __forceinline__ void finish_step(uint32_t mode, uint32_t *samples, Pa
             *(uint2 *)(samples + (size_t)2 * ps.item) = make_uint2(word, key);
         ps.phase = PH_IDLE;
         ps.d = mk(0.f, 0.f, 0.f);
-        ++done;
     }
 }
 
@@ -1404,9 +1410,9 @@ __device__ __forceinline__ void finish_step(uint32_t mode, uint32_t *samples, Pa
 // some thirty scalar mask instructions.  Two exec regions remain,
 // the scatter arithmetic and the refraction event, each lane's arithmetic and its order
 // unchanged.
-template <bool KARG, bool WT, bool SAMPLER>
+template <bool KARG, bool WT, bool SAMPLER, class CNT>
 __device__ __forceinline__ void shade_step_body(const RenderArgs &a, Path &ps, const Hit &h, bool act,
-                                                unsigned long long &done, unsigned long long &dropped, uint32_t *lds,
+                                                CNT &done, CNT &dropped, uint32_t *lds,
                                                 unsigned long long *diag_rounds)
 {
     // hit, shade and material tables are in slot order (spt_accel.cpp)
@@ -1502,9 +1508,9 @@ __device__ __forceinline__ void shade_step_body(const RenderArgs &a, Path &ps, c
     }
     finish_step<WT>(mode, samples, ps, endm | skym, mirm | refrm, refrm, trm, word, done, dropped);
 }
-template <bool KARG = false, bool WT = false>
+template <bool KARG = false, bool WT = false, class CNT>
 __device__ __forceinline__ void shade_step(const RenderArgs &a, Path &ps, const Hit &h, bool act,
-                                           unsigned long long &done, unsigned long long &dropped, uint32_t *lds,
+                                           CNT &done, CNT &dropped, uint32_t *lds,
                                            unsigned long long *diag_rounds = nullptr)
 {
     if (SPT_DUP & 128) {
@@ -1515,7 +1521,7 @@ __device__ __forceinline__ void shade_step(const RenderArgs &a, Path &ps, const 
         p2.d = opaque_v3(p2.d);
         Hit h2 = h;
         h2.t = opaque_v(h2.t);
-        unsigned long long d2 = 0, x2 = 0;
+        CNT d2 = 0, x2 = 0;
         shade_step_body<KARG, WT, false>(a, p2, h2, act, d2, x2, lds, nullptr);
         sink_v(p2.o.x);
         sink_v(p2.d.x);

@@ -85,7 +85,7 @@ __device__ __forceinline__ void trace_body(const TraceArgs &a)
     ps.slot = 0;
     ps.job = 0;
     uint32_t casts = 0;                         // of the lane's current path
-    unsigned long long done = 0, dropped = 0;  // shade_step's launch counters: not reported
+    uint32_t done = 0, dropped = 0;  // shade_step's launch counters: not reported
     CastDiag dg;
 
     for (;;) {

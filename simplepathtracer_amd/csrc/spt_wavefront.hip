@@ -94,7 +94,8 @@ __global__ __launch_bounds__(kWfBlock) void wf_render(WfArgs w)
     const size_t q0 = (size_t)blockIdx.x * w.qcap;
     const WfQueue q{w.q.o + q0, w.q.d + q0, w.q.m + q0};
     uint32_t len = 0;  // rays queued (block-uniform)
-    unsigned long long cast = 0, finished = 0, done = 0, dropped = 0;
+    unsigned long long cast = 0, finished = 0;
+    uint32_t done = 0, dropped = 0;  // finish_step's wave counts (a launch's items are 32-bit)
     for (;;) {
         // top-up: claim qcap - len items (the counter may run past n_items)
         if (tid == 0) s_claim = __hip_atomic_fetch_add((gu32 *)w.state, w.qcap - len, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -209,7 +210,7 @@ __global__ __launch_bounds__(kWfBlock) void wf_render(WfArgs w)
         atomicAdd(&a.counters[0], cast);
         atomicAdd(&a.counters[1], finished);
     }
-    if (dropped) atomicAdd(&a.counters[2], dropped);  // task mode only, rare
+    if (lane == 0 && dropped) atomicAdd(&a.counters[2], (unsigned long long)dropped);  // the wave's count (finish_step); task mode only, rare
 }
 
 template <bool TREE, int LEAF, bool GLANE>
