@@ -450,7 +450,8 @@ SPT_API int spt_render_samples(spt_ctx *ctx, int mode, uint32_t yBegin, uint32_t
 /* ---- ray queries: batched FindClosestIntersectionSphere (Collision.hpp:87-109) ---------
  * The closest sphere of rays the caller chooses, cast with the render's own traversals
  * of the current culling shape (spt_set_cluster_size / spt_set_cluster_tree; results are
- * identical for any): picking, object-id / depth / normal buffers, visibility queries.
+ * identical for any): picking, object-id / depth / normal buffers.  ("Is anything between
+ * these two points?" is spt_occluded_rays, below.)
  * Rays are float4 {ox, oy, oz, -} and {dx, dy, dz, -}; the w lanes are ignored.
  * idx[i] = the ORIGINAL index of ray i's closest sphere, or the scene's sphere count on a
  *   miss (what the reference returns: g_sphereNumber).
@@ -472,6 +473,42 @@ SPT_API int spt_cast_rays(spt_ctx *ctx, const float *origins4, const float *dirs
  * the directions (float4, w = 0).  SPT_ERR_ARG for x >= width, y >= height or s >= spp. */
 SPT_API int spt_primary_hits(spt_ctx *ctx, const uint32_t *xys, uint32_t n, uint32_t *idx, float *hit /*nullable*/,
                              float *dirs4 /*nullable*/);
+
+/* ---- occlusion queries: any-hit with a per-ray distance limit --------------------------
+ * Line of sight, shadow rays for a caller's own lighting, ambient occlusion, picking
+ * through a range.  For ray i with origin o, direction d and limit L (an fp32 SQUARED
+ * distance, as the reference's distanceSq):
+ *   occ[i] = 1  iff  idx_i < sphere count  and  ds_i < L   (fp32 compare)
+ *   occ[i] = 0  otherwise
+ * with (idx_i, ds_i) exactly what spt_cast_rays returns for (o, d) (ds: the second float4's
+ * w).  FindClosestIntersectionSphere returns the passing sphere of least distanceSq, so this
+ * is "some sphere passes with distanceSq < L": an any-hit query, answered by a walk that is
+ * bounded by L from its first node and ends at the first blocker.  Hence:
+ *   - L that is NaN or <= 0 gives 0;
+ *   - L >= FLT_MAX (+inf included) gives "hits anything": the reference never accepts
+ *     ds == FLT_MAX as a hit;
+ *   - L == ds gives 0: the compare is strict;
+ *   - the answer depends on neither the culling shape nor the walk;
+ *   - RaySphereIntersection's 1e-3 thresholds apply as to a cast: a ray leaving a sphere's
+ *     surface outward is not blocked by that sphere.
+ * flags == 0: a4 and b4 are origins and directions (float4, w ignored), L_i = limits[i],
+ *   or +inf where limits is null; scale is not read.
+ * SPT_OCCLUDE_SEGMENTS: a4 and b4 are end points a and b; limits must be null
+ *   (SPT_ERR_ARG otherwise).  v = b - a per component in fp32, o = a, d = Normalize(v) (the
+ *   shading path's), L = ((vx vx + vy vy) + vz vz) * scale without contraction;
+ *   scale = 1.0f leaves it unchanged.  a == b gives L = 0 and the answer 0.  A target point
+ *   b ON a sphere has ds ~ L for that sphere, either side of it by rounding: callers who mean
+ *   "up to but not including the target" pass a scale slightly below 1.
+ * Any other flag bit is SPT_ERR_ARG.  occ is n bytes, each 0 or 1.  As spt_cast_rays they
+ * need a scene only, use member 0 of a multi-device context, end a resident render-service
+ * session first, and leave spt_stats untouched.  n == 0 is SPT_OK and touches nothing. */
+#define SPT_OCCLUDE_SEGMENTS 1u
+/* device pointers, asynchronous on `stream` (NULL = default stream) */
+SPT_API int spt_occluded_rays_async(spt_ctx *ctx, const void *d_a4, const void *d_b4, const void *d_limits /*nullable*/,
+                                    uint32_t n, uint32_t flags, float scale, void *d_occ /* n bytes */, void *stream);
+/* host pointers, blocking; staged in chunks (at most 256 MiB of staging, as spt_cast_rays) */
+SPT_API int spt_occluded_rays(spt_ctx *ctx, const float *a4, const float *b4, const float *limits /*nullable*/,
+                              uint32_t n, uint32_t flags, float scale, uint8_t *occ);
 
 /* ---- path queries: batched TraceAndSampleColor (SingleThreadPathTracer.hpp:94-112) -----
  * The colour along rays the caller chooses: other camera models, light and irradiance

@@ -24,6 +24,7 @@ TREE_AUTO = 0xFFFFFFFF  # spt_set_cluster_tree default
 CLUSTER_AUTO = 0xFFFFFFFF  # spt_set_cluster_size default
 ENGINE_MEGAKERNEL, ENGINE_WAVEFRONT = 0, 1
 SELFTEST_COLS = 16
+OCCLUDE_SEGMENTS = 1  # SPT_OCCLUDE_SEGMENTS
 
 
 class SptError(RuntimeError):
@@ -169,6 +170,8 @@ def lib() -> ctypes.CDLL:
         "spt_cast_rays_async": ([P, P, P, u32, P, P, P], I),
         "spt_cast_rays": ([P, P, P, u32, P, P], I),
         "spt_primary_hits": ([P, P, u32, P, P, P], I),
+        "spt_occluded_rays_async": ([P, P, P, P, u32, u32, f32, P, P], I),
+        "spt_occluded_rays": ([P, P, P, P, u32, u32, f32, P], I),
         "spt_trace_rays_async": ([P, P, P, P, u32, u32, P, P, P], I),
         "spt_trace_rays": ([P, P, P, P, u32, u32, P, P], I),
         "spt_sample_state": ([u64, u32, u32, u32, P], I),

@@ -12,6 +12,7 @@
 //   spt_service.cpp  the render service's host half (sessions, publication, flow control)
 //   spt_multi.cpp    multi-device frames (spt_render_frame) and page-locked g_data
 //   spt_cast.cpp     ray queries (spt_cast_rays[_async], spt_primary_hits)
+//   spt_occlude.cpp  occlusion queries (spt_occluded_rays[_async])
 //   spt_trace.cpp    path queries (spt_trace_rays[_async], spt_sample_state)
 //   spt_features.cpp feature buffers (spt_render_features[_async])
 //   spt_denoise.cpp  the denoiser (spt_denoise[_async], spt_denoise_var[_async])

@@ -547,6 +547,22 @@ struct CastArgs {
 };
 hipError_t launch_cast(const CastArgs &a, hipStream_t s);
 
+// ---- occlusion queries (spt_occlude.hip; spt_occluded_rays[_async]) --------------------
+// n rays, one per lane: occ[i] = 1 iff the cast of ray i would hit with ds < L_i (DESIGN.md
+// §4.17), else 0.  Ray form: origins a, directions b, L_i = limits[i] (+inf where limits is
+// null).  Segment form: end points a and b; o = a, d = normalize(b - a), L = lensq(b - a) *
+// scale.
+struct OccludeArgs {
+    AccelView accel;
+    uint32_t n;
+    uint32_t segments;
+    float scale;
+    const float4 *a, *b;
+    const float *limits;
+    uint8_t *occ;
+};
+hipError_t launch_occlude(const OccludeArgs &a, hipStream_t s);
+
 // ---- path queries (spt_trace.hip; spt_trace_rays[_async]) ------------------------------
 // n paths, one per lane: TraceAndSampleColor(d[i], o[i], bounces) in segment semantics,
 // every draw of path i from the raw splitmix state st[i].  The trace kernel leaves path

@@ -468,13 +468,21 @@ __device__ __forceinline__ void test_leaf_pre(cfloat *slots, cfloat *kpre, const
 // of the wave's majority direction octant with the line, front and near tests.
 // LDSN (tree only): the node records are read from the block's LDS copy of layout 0
 // (`lnodes`, render_kernel's prologue) instead of scalar loads of the octant layouts.
-template <bool TREE, int LEAF, bool LDSN = false>
+// ANY (spt_occlude.hip; scalar records only): the bounded any-hit walk.
+// The lane's bound starts at `limit` (finite, >= 0; 0 for inactive lanes) with no winner,
+// so only a member with ds < limit is ever taken; a lane that took one is decided -- it
+// leaves every node mask -- and the walk ends when no active lane is undecided.  Only
+// idx == kMiss or not means anything then.  Every ANY line is behind `if constexpr`: the
+// closest-hit instances compile to the code they had.
+template <bool TREE, int LEAF, bool LDSN = false, bool ANY = false>
 __device__ __forceinline__ Hit find_closest(const AccelView &ac, const f3 &o, const f3 &d, bool active,
-                                            CastDiag &dg, const uint32_t *lnodes = nullptr, uint32_t *scratch = nullptr)
+                                            CastDiag &dg, const uint32_t *lnodes = nullptr, uint32_t *scratch = nullptr,
+                                            float limit = FLT_MAX)
 {
+    static_assert(!(ANY && LDSN), "the any-hit walk reads scalar records");
     Hit h;
     h.idx = kMiss;
-    h.best = FLT_MAX;
+    h.best = ANY ? limit : FLT_MAX;
     h.t = 0.f;
     const float dod = dot(o, d);
     cfloat *slots = (cfloat *)ac.slots;
@@ -508,6 +516,12 @@ __device__ __forceinline__ Hit find_closest(const AccelView &ac, const f3 &o, co
     }
     const unsigned long long live_mask = __ballot(active);
     cuint *nodes = (cuint *)ac.nodes;
+    // ANY: the active lanes without a blocker yet
+    unsigned long long undecided = live_mask;
+    if constexpr (ANY) {
+        undecided = live_mask & __ballot(h.idx == kMiss);
+        if (undecided == 0ull) return h;
+    }
     if (!TREE) {
         // flat list: node i is leaf i.  The line test in expanded form, with FMAs
         // (a conservative test need not follow the reference's operation order;
@@ -533,7 +547,7 @@ __device__ __forceinline__ Hit find_closest(const AccelView &ac, const f3 &o, co
         // qo = +inf (never pass) and lanes that must not cull carry -inf (always
         // pass), so the ballot of the compare is the node mask: about 5 SALU per node
         // instead of 17.
-        const float qoe = !active ? INFINITY : (no_cull ? -INFINITY : qo);
+        float qoe = !active ? INFINITY : (no_cull ? -INFINITY : qo);
         // member pretest terms: the node test's -2c o and qoe, plus the tc slack
         // mt = 2e-6 (pre_cm + |o|) + 1e-6 folded into -o.d
         const float olen = __builtin_amdgcn_sqrtf(oo) * 1.000001f;
@@ -543,6 +557,13 @@ __device__ __forceinline__ Hit find_closest(const AccelView &ac, const f3 &o, co
         pl.osz = osz;
         pl.qoe = qoe;
         pl.tinit = !active ? -INFINITY : (no_cull ? INFINITY : __builtin_fmaf(2e-6f, ac.pre_cm + olen, 1e-6f) - dod);
+        if constexpr (ANY) {
+            // lanes the always-list decided
+            const bool dec = h.idx != kMiss;
+            qoe = dec ? INFINITY : qoe;
+            pl.qoe = qoe;
+            pl.tinit = dec ? -INFINITY : pl.tinit;
+        }
         // c |Cb|^2 is left out of the sum: the node's threshold is K1'' = K1' - c |Cb|^2
         // (one rounding fewer)
         auto node_x = [&](const uint32_t *r) {
@@ -557,6 +578,17 @@ __device__ __forceinline__ Hit find_closest(const AccelView &ac, const f3 &o, co
             const unsigned long long mm = __ballot(!(x > __uint_as_float(r[6])));
             diag_node(mm);
             if (mm != 0ull) test_leaf_pre<LEAF>(slots, (cfloat *)ac.kpre, ac.orig, r[5], o, d, dod, pl, h, dg);
+            if constexpr (ANY) {
+                // decided lanes take the inactive lanes' terms: they pass no node and no
+                // member pretest from here on
+                if (mm != 0ull) {
+                    const bool dec = h.idx != kMiss;
+                    qoe = dec ? INFINITY : qoe;
+                    pl.qoe = qoe;
+                    pl.tinit = dec ? -INFINITY : pl.tinit;
+                    undecided &= ~__ballot(dec);
+                }
+            }
         };
         // The next record's load is issued only after this record's first use: a
         // scalar-load wait is lgkmcnt(0), so an earlier issue would be waited for here.
@@ -585,6 +617,9 @@ __device__ __forceinline__ Hit find_closest(const AccelView &ac, const f3 &o, co
             finish(rb, xb);
             p += 16;
             left -= 2u;
+            if constexpr (ANY) {
+                if (undecided == 0ull) return h;
+            }
         }
         if (left != 0u) finish(ra, node_x(ra));
         return h;
@@ -626,14 +661,16 @@ __device__ __forceinline__ Hit find_closest(const AccelView &ac, const f3 &o, co
     const float kn = active ? __builtin_fmaf(1e-5f, obs, 1e-6f) : -INFINITY;
     // tree node masks are (ballot(test) & live) | nocull: the ballot of a compare is
     // the compare's own lane mask, with no VALU round trip
-    const unsigned long long tree_nocull =
+    unsigned long long tree_nocull =
         (__ballot(!(ddev <= 1e-6f && ddev >= -1e-6f)) | __ballot(!(oo <= 1e30f))) & live_mask;
+    if constexpr (ANY) tree_nocull &= undecided;
     // near bound of the lane's current winner, refreshed after every leaf test;
     // ~1.8e19 while there is none (best = FLT_MAX: never culls)
     auto near_bound = [&](float best) {
         return __builtin_fmaf(__builtin_amdgcn_sqrtf(best), 1.00001f, kn);
     };
     float sbl = near_bound(h.best);
+    if constexpr (ANY) sbl = h.idx != kMiss ? -INFINITY : sbl;  // decided by the always-list
     // n nodes stepped, the last of them with mask mm
     auto diag_node = [&](uint32_t n, unsigned long long mm, bool leaf) {
         if (SPT_DIAG) {
@@ -683,6 +720,14 @@ __device__ __forceinline__ Hit find_closest(const AccelView &ac, const f3 &o, co
         }
         leaf_test(o, d, h);
         sbl = near_bound(h.best);
+        if constexpr (ANY) {
+            // a decided lane's bound collapses to the inactive lanes' -inf (t_f < t_n at
+            // every node) and it leaves the never-culling lanes
+            const bool dec = h.idx != kMiss;
+            sbl = dec ? -INFINITY : sbl;
+            undecided &= ~__ballot(dec);
+            tree_nocull &= undecided;
+        }
     };
     // the SPT_DUP & 8 copy of the node test (issue attribution builds)
     auto dup_node = [&](float lx, float ly, float lz, float hx, float hy, float hz) {
@@ -812,6 +857,9 @@ __device__ __forceinline__ Hit find_closest(const AccelView &ac, const f3 &o, co
             diag_node(nn, mm, slot != kNoSlot);
             if (slot == kNoSlot) break;
             enter_leaf(slot, mm);
+            if constexpr (ANY) {
+                if (undecided == 0ull) break;
+            }
         }
         return h;
     }

@@ -1,4 +1,4 @@
-// spt_query.h -- what the query kernels share (spt_cast.hip, spt_trace.hip,
+// spt_query.h -- what the query kernels share (spt_cast.hip, spt_occlude.hip, spt_trace.hip,
 // spt_features.hip): each family is five kernels, one per walk of cast_walk
 // (spt_internal.h), over a body of its own.  Here: the walk a body is compiled for, the
 // block's LDS copy of node layout 0, the cast that goes with the walk, and the launcher

@@ -1,5 +1,5 @@
 // spt_staging.h -- device staging of the blocking queries (spt_cast_rays, spt_primary_hits,
-// spt_trace_rays, spt_render_features, spt_denoise, spt_denoise_var, spt_render_moments,
+// spt_occluded_rays, spt_trace_rays, spt_render_features, spt_denoise, spt_denoise_var, spt_render_moments,
 // spt_render_adaptive, spt_temporal): one
 // device allocation cut into the arrays of a chunk of the call's items (rays, rows of
 // pixels, or the whole image), which the call copies in, launches over and copies out chunk
@@ -59,6 +59,13 @@ inline StagingPlan staging_plan(const StagingArray *arrays, int n_arrays, size_t
 inline StagingPlan cast_rays_plan(size_t n, bool hit)
 {
     const StagingArray a[4] = {{16}, {16}, {4}, {32, hit}};
+    return staging_plan(a, 4, n, StagingItems::kRays);
+}
+// spt_occluded_rays, per ray: origin, direction or end point in (+ the limit in); one byte
+// out, last (a chunk is whole waves, so but for the call's last chunk it is a multiple of 16)
+inline StagingPlan occluded_rays_plan(size_t n, bool limits)
+{
+    const StagingArray a[4] = {{16}, {16}, {4, limits}, {1, true, true}};
     return staging_plan(a, 4, n, StagingItems::kRays);
 }
 // spt_primary_hits, per ray: the (x, y, s) triple in; index (+ hit record, + direction) out

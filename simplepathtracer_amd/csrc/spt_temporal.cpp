@@ -81,10 +81,23 @@ int temporal_check(spt_ctx *ctx, const TemporalCall &c, spt::TemporalArgs *a, bo
       ins[9] = {{c.rgba, npix * 16u, "rgba"}, {c.mom, npix * 16u, "mom"}, {c.feat, npix * 32u, "feat"}, {c.ids, npix * 4u, "ids"},
                 {c.h_rgba, npix * 16u, "hist_rgba"}, {c.h_mom, npix * 16u, "hist_mom"}, {c.h_feat, npix * 32u, "hist_feat"},
                 {c.h_ids, npix * 4u, "hist_ids"}, {c.n_spheres ? c.motion : nullptr, (uint64_t)c.n_spheres * 32u, "motion"}};
+    // An output that overlaps one buffer usually runs on into whatever the allocator placed
+    // beside it, so several overlaps can hold at once.  The one named must not depend on
+    // those neighbours: first the motion table (the one input that is no image plane: an
+    // output may reach it with its last bytes only), then the buffer an output BEGINS in --
+    // an input before the other output --, then any other overlap in argument order.
+    const auto begins_in = [](const void *o, const void *p, uint64_t n) { return overlaps(o, 1, p, n); };
+    for (const auto &o : outs)
+        if (overlaps(o.p, o.n, ins[8].p, ins[8].n)) return fail(ctx, SPT_ERR_ARG, "%s overlaps %s", o.name, ins[8].name);
+    for (const auto &o : outs)
+        for (const auto &i : ins)
+            if (begins_in(o.p, i.p, i.n)) return fail(ctx, SPT_ERR_ARG, "%s overlaps %s", o.name, i.name);
+    if (begins_in(outs[0].p, outs[1].p, outs[1].n) || begins_in(outs[1].p, outs[0].p, outs[0].n))
+        return fail(ctx, SPT_ERR_ARG, "out_rgba overlaps out_mom");
     for (const auto &o : outs)
         for (const auto &i : ins)
             if (overlaps(o.p, o.n, i.p, i.n)) return fail(ctx, SPT_ERR_ARG, "%s overlaps %s", o.name, i.name);
-    if (overlaps(outs[0].p, outs[0].n, outs[1].p, outs[1].n)) return fail(ctx, SPT_ERR_ARG, "out_rgba overlaps out_mom");
+    // (two overlapping outputs: the later one begins in the earlier, caught above)
     a->width = c.W;
     a->height = c.H;
     a->fw = (float)c.W;

@@ -306,6 +306,51 @@ class Context:
                                                       ctypes.c_void_p(d_idx or None), ctypes.c_void_p(d_hit or None),
                                                       ctypes.c_void_p(stream or None)))
 
+    def _occluded(self, a, b, limits, flags, scale) -> np.ndarray:
+        occ = np.zeros(len(a), np.uint8)
+        self._check(_native.lib().spt_occluded_rays(self._h, _p(a), _p(b), _p(limits) if limits is not None else None,
+                                                    len(a), flags, float(scale), _p(occ)))
+        return occ.astype(bool)
+
+    def occluded(self, origins, dirs, limit_sq=None) -> np.ndarray:
+        """Any-hit with a distance limit (spt_occluded_rays): for n rays, (n, 3) or (n, 4)
+        float arrays (w ignored), whether cast_rays would hit a sphere with ds < limit_sq --
+        a SQUARED distance, fp32, a scalar or an (n,) array; None: unbounded.  Returns an (n,)
+        bool array.  NaN and <= 0 limits give False; the compare is strict."""
+        o, d = self._rays4(origins, "origins"), self._rays4(dirs, "dirs")
+        if len(o) != len(d):
+            raise ValueError(f"{len(o)} origins for {len(d)} directions")
+        lim = None
+        if limit_sq is not None:
+            lim = np.asarray(limit_sq, np.float32)
+            if lim.ndim == 0:
+                lim = np.full(len(o), lim, np.float32)
+            lim = np.ascontiguousarray(lim.reshape(-1))
+            if len(lim) != len(o):
+                raise ValueError(f"{len(lim)} limits for {len(o)} rays")
+        return self._occluded(o, d, lim, 0, 1.0)
+
+    def visible(self, a, b, scale=1.0) -> np.ndarray:
+        """Line of sight between the points a[i] and b[i], (n, 3) or (n, 4) float arrays:
+        True where no sphere blocks the segment (spt_occluded_rays with
+        SPT_OCCLUDE_SEGMENTS, negated): the ray from a along Normalize(b - a), limited to
+        |b - a|^2 * scale.  A b on a sphere's surface lies at that sphere's own distance to
+        within rounding: pass a scale slightly below 1 to leave the target out."""
+        pa, pb = self._rays4(a, "a"), self._rays4(b, "b")
+        if len(pa) != len(pb):
+            raise ValueError(f"{len(pa)} points a for {len(pb)} points b")
+        return ~self._occluded(pa, pb, None, _native.OCCLUDE_SEGMENTS, scale)
+
+    def occluded_async(self, d_a, d_b, d_limits, n, d_occ, segments=False, scale=1.0, stream=0) -> None:
+        """Device-resident occluded / visible (spt_occluded_rays_async): raw device pointers
+        to n float4 origins and directions (segments=True: end points a and b), n fp32
+        squared limits (0: unbounded; must be 0 with segments) and n answer bytes (1 =
+        occluded), enqueued on `stream` (a hipStream_t; 0 = the default stream)."""
+        self._check(_native.lib().spt_occluded_rays_async(
+            self._h, ctypes.c_void_p(d_a or None), ctypes.c_void_p(d_b or None), ctypes.c_void_p(d_limits or None), int(n),
+            _native.OCCLUDE_SEGMENTS if segments else 0, float(scale), ctypes.c_void_p(d_occ or None),
+            ctypes.c_void_p(stream or None)))
+
     def primary_hits(self, xys, hits=False, dirs=False):
         """The closest sphere of the primary ray of sample s of pixel (x, y), for every
         (x, y, s) row of xys (spt_primary_hits; the render's own ray).  Returns idx, followed
